@@ -7,10 +7,18 @@ A secondary line item times the Q-Former caption step (B=128 per GPU, accumulati
 SURVEY.md D6) — the north star's roofline target.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload lm|qformer|linear|cross]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write
+the outputs of the last timed step (--dump-outputs), print the line.  --full adds everything
+else the bench measures, as extra runs after the timed region: the eager per-GEMM pass behind
+`roofline`, the caption-step lines, the pixel-input line and the CPU baselines (each of which
+its own --no-* option still switches off).
+
 Prints ONE JSON line (rank 0).  Inputs are synthetic (random tokens / N(0,1) CLIP tokens),
-resident in HBM before timing; weights random-init with the reference's init recipe.
+seeded (the same arguments give the same inputs and initial weights in every run), resident
+in HBM before timing; weights random-init with the reference's init recipe.
 """
 from __future__ import annotations
 
@@ -255,10 +263,11 @@ def kernel_pass(step, first_it, steps, timer):
     torch.cuda.synchronize()
 
 
-def timed(step, steps, warmup, world, timer=None, graph=False, kernel_steps=1):
+def timed(step, steps, warmup, world, timer=None, graph=False, kernel_steps=1, dump=None):
     """Time exactly `steps` steps (barrier + synchronize on both sides, max over ranks);
-    then, outside the timed region, one eager kernel pass of `kernel_steps` steps with the
-    per-GEMM dispatch timer (the roofline line)."""
+    then, outside the timed region, `dump(result)` of the last timed step (--dump-outputs)
+    and, with a `timer`, one eager kernel pass of `kernel_steps` steps with the per-GEMM
+    dispatch timer (the roofline line)."""
     eager = step
     if graph:
         step = graphed(step, warmup)
@@ -283,9 +292,39 @@ def timed(step, steps, warmup, world, timer=None, graph=False, kernel_steps=1):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     loss, norm = float(r.loss), float(r.norm)  # read before the kernel pass moves the model
+    if dump is not None:
+        dump(r)
     if timer is not None:
         kernel_pass(eager, warmup + steps, kernel_steps, timer)
     return dt, (loss, norm)
+
+
+DUMP_SEED = 20240607
+DUMP_PER_TENSOR = 32768          # sampled elements of each parameter tensor
+DUMP_BUDGET_BYTES = 48 << 20     # of float32, all tensors together (the files stay < 64 MB)
+
+
+def dump_outputs(path, result, model):
+    """--dump-outputs: what a caller of the timed step holds after its last call, as float32
+    .npy files: loss.npy and grad_norm.npy (the StepResult) and params.npy, the updated
+    parameters in named_parameters() order, each tensor whole when small, else a fixed
+    seeded sample of its elements (sorted indices, the same in every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("loss", result.loss), ("grad_norm", result.norm)):
+        np.save(os.path.join(path, name + ".npy"),
+                t.detach().float().reshape(1).cpu().numpy())
+    params = [p for _, p in model.named_parameters()]
+    per = min(DUMP_PER_TENSOR, DUMP_BUDGET_BYTES // 4 // max(1, len(params)))
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(0, flat.numel(), (per,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params.npy"), torch.cat(parts).numpy())
 
 
 TRAFFIC_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_traffic.json")
@@ -457,8 +496,17 @@ def main():
     ap.add_argument("--caption-batch", type=int, default=128)
     ap.add_argument("--bucket-mb", type=float, default=None,
                     help="gradient bucket size (default: 32 MB for the LM, 8 MB for the captions)")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, grad norm and "
+                         "(sampled) updated parameters to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-GEMM "
+                         "roofline pass, the caption-step and pixel-input lines, the CPU "
+                         "baselines (see the --no-* options)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the caption-step and pixel-input lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--caption-steps", type=int, default=10)
     ap.add_argument("--captions", default="qformer,linear,cross",
                     help="secondary caption-step lines of the default (lm) run")
@@ -467,9 +515,10 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
                     help="CPU work per cpu_baseline sample (LM; captions get half)")
     ap.add_argument("--no-kernel-pass", action="store_true",
-                    help="skip the eager per-GEMM timing pass (profiling runs)")
+                    help="with --full: skip the eager per-GEMM timing pass (profiling runs)")
     ap.add_argument("--gemm-table", action="store_true",
-                    help="list every GEMM instance of the step in roofline.all_gemms")
+                    help="with --full: list every GEMM instance of the step in "
+                         "roofline.all_gemms")
     ap.add_argument("--no-graph", action="store_true",
                     help="eager steps (default: the step is captured into hipGraphs; at N>1 two "
                          "graphs around the RCCL gradient all-reduce)")
@@ -487,8 +536,14 @@ def main():
         step, units, cfg = run_caption(args.workload, args, world, rank, dev)
         unit, flop_per_unit = "images/s", CAP_FLOP_PER_IMAGE[args.workload]
     use_graph = not args.no_graph
-    timer = None if args.no_kernel_pass else K.KernelTimer()
-    dt, res = timed(step, args.steps, args.warmup, world, timer, graph=use_graph)
+    kernel_pass_on = args.full and not args.no_kernel_pass
+    secondary = args.full and not args.no_secondary
+    cpu_lines = args.full and not args.no_cpu_baseline
+    timer = K.KernelTimer() if kernel_pass_on else None
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda r: dump_outputs(args.dump_outputs, r, step.graph_args[0])  # noqa: E731
+    dt, res = timed(step, args.steps, args.warmup, world, timer, graph=use_graph, dump=dump)
     value = units * args.steps / dt
     roof = dominant_kernel(timer.summary(), args.workload, steps=1, full=args.gemm_table) if timer else None
     out = {
@@ -504,15 +559,15 @@ def main():
         "peak_hbm_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
         "roofline": roof,
     }
-    if args.workload == "lm" and not args.no_secondary:
-        del step
+    if args.workload == "lm" and secondary:
+        del step, dump
         torch.cuda.empty_cache()
         for kind in args.captions.split(","):
             if not kind:
                 continue
             torch.cuda.reset_peak_memory_stats(dev)
             cstep, cunits, ccfg = run_caption(kind, args, world, rank, dev)
-            ctimer = None if args.no_kernel_pass else K.KernelTimer()
+            ctimer = K.KernelTimer() if kernel_pass_on else None
             cdt, cres = timed(cstep, args.caption_steps, 3, world, ctimer, graph=use_graph,
                               kernel_steps=3)
             cval = cunits * args.caption_steps / cdt
@@ -525,15 +580,15 @@ def main():
                 peak_hbm_gib=round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
                 roofline=dominant_kernel(ctimer.summary(), kind, steps=3, full=args.gemm_table)
                 if ctimer else None)
-            if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            if rank == 0 and world == 1 and cpu_lines:
                 line["cpu_baseline"] = cpu_baseline(kind, seconds=args.cpu_seconds / 2)
             out[f"caption_{kind}"] = line
             del cstep
             torch.cuda.empty_cache()
-    if args.workload == "lm" and not args.no_secondary and args.pixels and world == 1:
+    if args.workload == "lm" and secondary and args.pixels and world == 1:
         out["caption_linear_pixels"] = run_pixels(args, world, rank, dev, args.caption_steps, 3)
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_lines:
         out["cpu_baseline"] = cpu_baseline(args.workload, seconds=args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

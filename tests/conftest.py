@@ -18,13 +18,13 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from tests.helpers import load_golden
 
     cache = {}
 
     def load(name):
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+            cache[name] = load_golden(name, GOLDEN)
         return cache[name]
 
     return load

@@ -1,6 +1,9 @@
 """Shared test helpers: recipe weights, fixture comparison, model builders."""
 from __future__ import annotations
 
+import glob
+import os
+
 import numpy as np
 import torch
 
@@ -8,6 +11,49 @@ from oracle import models as OM
 from oracle import weights as W
 
 TINY = dict(block_size=64, vocab_size=512, n_layer=2, n_head=2, n_embd=128)
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_FILE_LIMIT = 1 << 20  # no committed file is larger than 1 MiB
+
+
+def _golden_parts(name, root):
+    return sorted(glob.glob(os.path.join(root, glob.escape(name) + ".part[0-9][0-9].npz")))
+
+
+def load_golden(name, root=GOLDEN):
+    """The arrays of fixture `name`: one NAME.npz, or NAME.part00.npz, NAME.part01.npz, ...
+    holding consecutive runs of its arrays when one file would exceed the size limit."""
+    whole = os.path.join(root, name + ".npz")
+    paths = [whole] if os.path.exists(whole) else _golden_parts(name, root)
+    if not paths:
+        raise FileNotFoundError(f"no fixture {name} (.npz or .partNN.npz) in {root}")
+    out = {}
+    for p in paths:
+        with np.load(p) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
+def save_golden(name, arrays, compressed=True, root=GOLDEN, limit=GOLDEN_FILE_LIMIT):
+    """Write fixture `name` for load_golden: one file when it stays under `limit` bytes, else
+    the fewest equal-count runs of its arrays (in order) whose files all do."""
+    save = np.savez_compressed if compressed else np.savez
+    keys = list(arrays)
+    for old in [os.path.join(root, name + ".npz")] + _golden_parts(name, root):
+        if os.path.exists(old):
+            os.remove(old)
+    for n in range(1, len(keys) + 1):
+        per = -(-len(keys) // n)
+        paths = []
+        for i in range(0, len(keys), per):
+            part = name + (".npz" if n == 1 else f".part{i // per:02d}.npz")
+            paths.append(os.path.join(root, part))
+            save(paths[-1], **{k: arrays[k] for k in keys[i:i + per]})
+        if all(os.path.getsize(p) <= limit for p in paths):
+            return paths
+        for p in paths:
+            os.remove(p)
+    raise ValueError(f"fixture {name}: one array alone exceeds {limit} bytes")
 
 
 def recipe_params(keys_shapes, dtype=torch.float32, device="cpu"):
@@ -30,7 +76,6 @@ def margins_out(name, rec):
     """Write a parity test's measured errors as JSON under $GVL_MARGINS_DIR (default
     gpurun_out/parity_margins; the GPU session copies them into profiles/)."""
     import json
-    import os
     d = os.environ.get("GVL_MARGINS_DIR", os.path.join("gpurun_out", "parity_margins"))
     try:
         os.makedirs(d, exist_ok=True)

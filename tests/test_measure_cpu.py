@@ -62,3 +62,33 @@ def test_committed_traffic_covers_bench_dominant_kernels():
         b = json.load(f)
     for wl, name in (("lm", b["roofline"]["kernel"]), ("qf", b["caption_qformer"]["roofline"]["kernel"])):
         assert t[wl][name]["hbm_bytes"] > 0 and 0 < t[wl][name]["mfma_rate_frac"] < 1
+
+
+def test_dump_outputs_writes_seeded_float32_sample(tmp_path):
+    """bench.py --dump-outputs: loss, grad norm and the parameters (small tensors whole, large
+    ones as the same sorted sample in every call) as float32 .npy within the size budget."""
+    import numpy as np
+    import torch
+    bench = _load("bench", os.path.join(ROOT, "bench.py"))
+    from gvl.train import StepResult
+    torch.manual_seed(3)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 7)).to(torch.bfloat16)
+    r = StepResult(torch.tensor(2.5), torch.tensor(0.75))
+    per = bench.DUMP_PER_TENSOR
+    assert 300 * 200 > per > 200  # the first weight is sampled, the other tensors are whole
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), r, m)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["grad_norm.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss.npy"].tolist() == [2.5] and got["grad_norm.npy"].tolist() == [0.75]
+    p = got["params.npy"]
+    assert p.shape == (per + 200 + 200 * 7 + 7,)
+    w0 = m[0].weight.detach().float().reshape(-1).numpy()
+    assert np.isin(p[:per], w0).all()
+    np.testing.assert_array_equal(p[per:per + 200], m[0].bias.detach().float().numpy())
+    np.testing.assert_array_equal(p[-7:], m[1].bias.detach().float().numpy())
+    for f, v in got.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) < 64 << 20
+

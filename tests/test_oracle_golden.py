@@ -170,3 +170,25 @@ def test_fast_paths_match_explicit_math():
             O.FAST_PATHS = False
     for a, b_ in zip(*outs):
         assert torch.allclose(a, b_, rtol=1e-5, atol=1e-5)
+
+
+def test_golden_fixture_split_round_trip(tmp_path):
+    """tests.helpers.save_golden splits a fixture over the size limit into .partNN.npz files
+    that load_golden merges back in order; no committed fixture exceeds the limit."""
+    import os
+
+    from tests.helpers import GOLDEN, GOLDEN_FILE_LIMIT, load_golden, save_golden
+    rng = np.random.default_rng(0)
+    arrays = {f"a{i}": rng.integers(0, 256, 3000 + i, dtype=np.uint8) for i in range(7)}
+    arrays["f"] = rng.standard_normal((5, 3)).astype(np.float32)
+    one = save_golden("whole", arrays, root=str(tmp_path))
+    parts = save_golden("split", arrays, root=str(tmp_path), limit=9000)
+    assert len(one) == 1 and len(parts) > 1
+    assert all(os.path.getsize(p) <= 9000 for p in parts)
+    for name in ("whole", "split"):
+        got = load_golden(name, str(tmp_path))
+        assert list(got) == list(arrays)
+        for k, v in arrays.items():
+            assert got[k].dtype == v.dtype and np.array_equal(got[k], v)
+    for fn in os.listdir(GOLDEN):
+        assert os.path.getsize(os.path.join(GOLDEN, fn)) <= GOLDEN_FILE_LIMIT, fn

@@ -11,7 +11,8 @@ import gvl._lib as L; L.load()
 
 # 2) linear full-size step detail
 meta = json.load(open(os.path.join(ROOT, "tests/golden/meta.json")))
-fx = dict(np.load(os.path.join(ROOT, "tests/golden/full_train.npz")))
+from tests.helpers import load_golden
+fx = load_golden("full_train")
 for kind in ("lm",):
     model, P = _recipe(_build_full(kind), cuda)
     model.eval()

@@ -9,7 +9,8 @@ Loads (read-only, at run time):
 Weights come from the library-independent recipe in oracle/weights.py; bridges run in
 eval() (dropout off) but still take gradients; cross_gate is non-zero.
 
-Writes tests/golden/*.npz (+ meta.json).  Usage: python tools/make_fixtures.py [--full]
+Writes tests/golden/*.npz (+ meta.json); a fixture that would exceed 1 MiB is written as
+NAME.partNN.npz files (tests/helpers.py save_golden).  Usage: python tools/make_fixtures.py [--full]
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import weights as W  # noqa: E402
+from tests.helpers import save_golden  # noqa: E402
 
 REF = "/root/reference/source"
 OUT = os.path.join(ROOT, "tests", "golden")
@@ -179,7 +181,7 @@ def fixture_gpt(g2, meta):
     out["greedy_prompt"] = x[:1, :8].numpy()
     out["greedy_tokens"] = toks.numpy()
     out["greedy_margins"] = margins.numpy()
-    np.savez(os.path.join(OUT, "gpt_tiny.npz"), **out)
+    save_golden("gpt_tiny", out, compressed=False, root=OUT)
 
 
 def fixture_caption(mod, kind, meta, m_vis):
@@ -217,7 +219,7 @@ def fixture_caption(mod, kind, meta, m_vis):
     out["greedy_prompt"] = x[:1, :3].numpy()
     out["greedy_tokens"] = toks.numpy()
     out["greedy_margins"] = margins.numpy()
-    np.savez(os.path.join(OUT, f"{kind}_tiny.npz"), **out)
+    save_golden(f"{kind}_tiny", out, compressed=False, root=OUT)
 
 
 def fixture_cross(mod, meta):
@@ -256,7 +258,7 @@ def fixture_cross(mod, meta):
     # unmasked-loss variant too
     _, loss_plain = model(x, z=z, targets=y)
     out["loss_unmasked"] = np.array(float(loss_plain))
-    np.savez(os.path.join(OUT, "cross_tiny.npz"), **out)
+    save_golden("cross_tiny", out, compressed=False, root=OUT)
 
 
 def fixture_ops(lin_mod):
@@ -320,7 +322,7 @@ def fixture_ops(lin_mod):
     out["adam:g1"], out["adam:g2"] = grads[0].numpy(), grads[1].numpy()
     out["adam:p1_after"], out["adam:p2_after"] = ps[0].detach().numpy(), ps[1].detach().numpy()
     out["adam:norms"] = np.array(norms)
-    np.savez(os.path.join(OUT, "ops.npz"), **out)
+    save_golden("ops", out, compressed=False, root=OUT)
 
 
 def fixture_full(g2, qf_mod, meta):
@@ -352,7 +354,7 @@ def fixture_full(g2, qf_mod, meta):
     out["qf_gradnorm"] = np.array(float(norm))
     out["qf_x"], out["qf_labels"] = x.numpy(), labels.numpy()
     out["qf_z_seed"] = np.array(505)
-    np.savez(os.path.join(OUT, "full124m.npz"), **out)
+    save_golden("full124m", out, compressed=False, root=OUT)
 
 
 # ------------------------------------------------------------------ round-2 fixtures
@@ -495,7 +497,7 @@ def fixture_full_train(g2, lin, qf, xa, meta):
         print(pre, out[pre + "losses"], out[pre + "norms"], out[pre + "loss_after"], flush=True)
     out["z_seeds"] = np.array([606, 707])
     out["cap_batch"] = np.array(CAP_B)
-    np.savez_compressed(os.path.join(OUT, "full_train.npz"), **out)
+    save_golden("full_train", out, root=OUT)
 
 
 def fixture_accum(g2, qf, meta):
@@ -523,7 +525,7 @@ def fixture_accum(g2, qf, meta):
     train_ref(model, mbs, lambda m, b: m(b[0], b[1], labels=b[2])[1], 2, 1e-3, out, "qformer_",
               names, mp=True)
     out["qformer_z_seeds"] = np.array([950 + i for i in range(4)])
-    np.savez_compressed(os.path.join(OUT, "accum_tiny.npz"), **out)
+    save_golden("accum_tiny", out, root=OUT)
 
 
 def fixture_edge(lin, qf, xa, meta):
@@ -563,7 +565,7 @@ def fixture_edge(lin, qf, xa, meta):
     out["cross_noz_logits_sq"] = np.array(float((logits.double() ** 2).sum()))
     out["x"], out["y"], out["labels"] = x.numpy(), yy.numpy(), labels.numpy()
     out["z_seed"] = np.array(202)
-    np.savez_compressed(os.path.join(OUT, "edge_tiny.npz"), **out)
+    save_golden("edge_tiny", out, root=OUT)
 
 
 def fixture_greedy(g2, lin, qf, xa, meta):
@@ -602,7 +604,7 @@ def fixture_greedy(g2, lin, qf, xa, meta):
         run(f"{size}_cross_", lambda s: m(s, z=z)[0], xc[:, :3])
         del model, m
     out["z_seed"] = np.array(1212)
-    np.savez_compressed(os.path.join(OUT, "greedy.npz"), **out)
+    save_golden("greedy", out, root=OUT)
 
 
 BENCH_CAP_B = 128   # bench.py caption batch
@@ -681,7 +683,7 @@ def fixture_bench_shapes(g2, lin, qf, xa, meta):
     out["lm_seed"] = np.array(4040)
     out["lm_batch"] = np.array(BENCH_LM_B)
     print("lm", float(loss), out["lm_loss_fp32w"], out["lm_gradnorm"], flush=True)
-    np.savez_compressed(os.path.join(OUT, "bench_shapes.npz"), **out)
+    save_golden("bench_shapes", out, root=OUT)
 
 
 def main():

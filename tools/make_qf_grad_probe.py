@@ -70,7 +70,7 @@ def main():
     for name, t in caught.items():
         sample(name, t.grad, out)
         print(name, tuple(t.shape), float(t.grad.double().norm()), flush=True)
-    np.savez_compressed(os.path.join(MF.OUT, "qf_grad_probe.npz"), **out)
+    MF.save_golden("qf_grad_probe", out, root=MF.OUT)
     print("loss", float(loss))
 
 

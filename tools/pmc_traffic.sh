@@ -17,7 +17,7 @@ for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI
     if [ $wl = lm ]; then a="--steps 1 --warmup 0 --no-secondary"
     else a="--workload $([ $wl = qf ] && echo qformer || echo $wl) --steps 2 --warmup 0"; fi
     timeout -s KILL 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/${wl}_$d -o run -- \
-      python bench.py $a --no-cpu-baseline --no-graph > $OUT/${wl}_$d.log 2>&1 || exit $?
+      python bench.py --full $a --no-cpu-baseline --no-graph > $OUT/${wl}_$d.log 2>&1 || exit $?
   done
 done
 python tools/pmc_traffic.py $OUT > gpurun_out/pmc_traffic_$TAG.json

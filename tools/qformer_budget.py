@@ -4,7 +4,7 @@ time, the MFMA floor (algorithmic FLOP at the 2516.6 TFLOP/s dense bf16 peak), t
 achievable step and its fraction of the bf16 roofline.
 
 python tools/qformer_budget.py BENCH_JSON KERNEL_TABLE
-  BENCH_JSON   bench.py --workload qformer --gemm-table line (exact GEMM FLOP per instance)
+  BENCH_JSON   bench.py --full --workload qformer --gemm-table line (exact GEMM FLOP per instance)
   KERNEL_TABLE tools/prof_table.py output of the same step (rocprofv3 --kernel-trace --stats,
                steps 10 + warmup 3 + 1 capture = 14 per-step launches per kernel)
 
