@@ -494,9 +494,13 @@ def sample(logits2, u, temperature=1.0, top_k=0, top_p=1.0, out=None):
 
 # ---------------------------------------------------------------------- cross entropy
 def cross_entropy(logits2, targets, *, rows_per_group=None, group_stride=0, row_offset=0,
-                  mask=None, mask_mode=False, want_grad=True, vocab=None):
+                  mask=None, mask_mode=False, want_grad=True, vocab=None, dlogits=None):
     """Returns (loss_and_inv [2] fp32 device tensor, dlogits [rows, V] bf16 or None).
-    `vocab` < logits2.shape[1] marks the trailing columns as padding (V % 8 != 0)."""
+    `vocab` < logits2.shape[1] marks the trailing columns as padding (V % 8 != 0): the kernel
+    writes the gradient of columns [0, ceil(vocab / 8) * 8), zero past `vocab`; any further
+    padding columns of the returned dlogits are zeroed here, so all of it can feed a GEMM.
+    `dlogits`: a caller's [rows, >= ceil(vocab / 8) * 8] bf16 row-major view to write instead
+    (only those columns of it are written)."""
     _dev(logits2, targets)
     Vp = logits2.shape[1]
     V = Vp if vocab is None else int(vocab)
@@ -511,7 +515,17 @@ def cross_entropy(logits2, targets, *, rows_per_group=None, group_stride=0, row_
     if mask is not None:
         mk = mask.reshape(-1).to(torch.uint8).contiguous()
     row_loss = torch.empty(max(rows, 1), dtype=F32, device=logits2.device)
-    dl = torch.empty(rows, Vp, dtype=BF16, device=logits2.device) if want_grad else None
+    dl = None
+    if dlogits is not None:
+        _rowmajor(dlogits, "dlogits")
+        if dlogits.dtype != BF16 or dlogits.shape[0] != rows:
+            raise ValueError("gvl.cross_entropy: dlogits must be bf16 with one row per target")
+        dl = dlogits
+    elif want_grad:
+        dl = torch.empty(rows, Vp, dtype=BF16, device=logits2.device)
+        vpad = (V + 7) // 8 * 8
+        if Vp > vpad:  # never in the product (pad_vocab pads to 8): the kernel stops at vpad
+            dl[:, vpad:].zero_()
     out = torch.empty(2, dtype=F32, device=logits2.device)
     _lib.check(_L().gvl_cross_entropy(logits2.data_ptr(), logits2.stride(0), rows, V,
                                       rows_per_group, group_stride, row_offset, tg.data_ptr(),

@@ -92,6 +92,84 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / den)
 
 
+def f64(t):
+    """A tensor or array as a float64 numpy array (exact for bf16 / fp32 values)."""
+    if isinstance(t, torch.Tensor):
+        return t.detach().to(torch.float64).cpu().numpy()
+    return np.asarray(t, dtype=np.float64)
+
+
+def rel_err_rows(a, b):
+    """rel_err per row: every row of the [..., cols] arrays is divided by its own max |b|; the
+    worst row is returned, so a row of small scale is not hidden behind a large one."""
+    a, b = f64(a), f64(b)
+    a = a.reshape(-1, a.shape[-1])
+    b = b.reshape(-1, b.shape[-1])
+    den = np.maximum(np.abs(b).max(axis=1), 1e-30)
+    return float((np.abs(a - b).max(axis=1) / den).max())
+
+
+def ulp_bf16(ref):
+    """The bf16 unit in the last place at |ref| (8 significand bits): 2**(floor(log2|ref|) - 7),
+    in float64, |ref| clamped below at 2**-126 (the smallest normal)."""
+    a = np.maximum(np.abs(f64(ref)), 2.0 ** -126)
+    return np.exp2(np.floor(np.log2(a)) - 7)
+
+
+F32_UNIT = 2.0 ** -24  # half an fp32 ulp, relative: the most one fp32 rounding adds
+
+
+def err_units(got, ref64, scale):
+    """max |got - ref64| in units of 2**-24 * scale (the measured `slack` of assert_f32_close)."""
+    err = np.abs(f64(got) - f64(ref64))
+    unit = F32_UNIT * np.abs(f64(scale))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(unit > 0, err / unit, np.where(err == 0, 0.0, np.inf))
+    r = np.where(np.isnan(r), np.inf, r)
+    return float(r.max()) if r.size else 0.0
+
+
+def _close(got, ref64, tol, ulp, name):
+    got, ref = f64(got), f64(ref64)
+    assert got.shape == ref.shape, f"{name}: shape {got.shape} vs {ref.shape}"
+    if got.size == 0:
+        return 0.0
+    fin = np.isfinite(ref)
+    same = (got == ref) | (np.isnan(got) & np.isnan(ref))  # a non-finite reference: identical
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - ref)
+        ok = np.where(fin, err <= tol, same)
+        excess = np.where(ok, 0.0, np.where(fin & np.isfinite(err), (err - tol) / ulp, np.inf))
+    if not ok.all():
+        i = tuple(int(k) for k in np.unravel_index(int(np.argmax(excess)), excess.shape))
+        raise AssertionError(
+            f"{name}: {int((~ok).sum())} of {ok.size} elements out of tolerance; worst at {i}: "
+            f"got {float(got[i])!r} want {float(ref[i])!r}, |diff| {err[i]:.6g} exceeds the bound "
+            f"{np.broadcast_to(tol, ref.shape)[i]:.6g} by {excess[i]:.3g} ulp")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.where(fin, err / ulp, 0.0).max())
+
+
+def assert_bf16_close(got, ref64, *, scale=None, slack=0, name=""):
+    """Every element of the bf16 result `got` within ulp_bf16(ref64) + slack * 2**-24 * scale of
+    the float64 reference.  One ulp is derived, not tuned: half an ulp is the final
+    round-to-nearest-even, the other half lets fp32 arithmetic in front of it flip a near-tie.
+    `scale` (an array: the sum of the absolute values of the terms that were added to form the
+    result) and `slack` (a count of fp32 roundings) matter only where the operation cancels.
+    Returns the worst error in ulps; on failure reports the worst element."""
+    ulp = ulp_bf16(ref64)
+    tol = ulp if scale is None else ulp + slack * F32_UNIT * np.abs(f64(scale))
+    return _close(got, ref64, tol, ulp, name or "bf16")
+
+
+def assert_f32_close(got, ref64, scale, slack, name=""):
+    """Every element of the fp32 result `got` within slack * 2**-24 * scale of the float64
+    reference (no ulp term).  Returns the measured error in those units."""
+    s = np.abs(f64(scale))
+    _close(got, ref64, slack * F32_UNIT * s, np.maximum(F32_UNIT * s, 2.0 ** -149), name or "f32")
+    return err_units(got, ref64, scale)
+
+
 def check_summary(fx, name, t, rtol):
     """Compare tensor t against the fixture summary of `name` (full or sampled + sums)."""
     a = t.detach().to(torch.float64).cpu().numpy().reshape(-1)

@@ -579,12 +579,15 @@ def _w4_name(M, K, epi, N=768, b_mn=0):
 @pytest.mark.parametrize("M,N,K", [(8064, 768, 3072), (8064, 768, 2304), (7992, 776, 192),
                                    (16384, 768, 384), (300, 128, 192), (8064, 3072, 768),
                                    (3968, 768, 3072), (4096, 768, 768), (3970, 776, 192),
-                                   (7992, 776, 384), (3970, 904, 768)])
+                                   (7992, 776, 384), (3970, 904, 768), (3968, 744, 768)])
 def test_gemm_w4(cuda, b_mn, epi, M, N, K):
     """Four-wave 192x128 / 128x128 deep-ring kernel (gemm_w4.hip), forced with gvl_gemm_tune(3, 10):
     the caption decoder's N = 768 shapes (252 tiles, one per CU), ragged M and N (N % 128 != 0),
     several tiles per workgroup with the ring running across tiles (516 tiles), a tile grid
-    smaller than the ring, and every epilogue kind."""
+    smaller than the ring, and every epilogue kind.  (3968, 744, 768): 248 tiles of 128 x 96
+    (gemm_w4n_kernel; 96 x 128 gemm_w4r_kernel for the plain MN-contiguous B) whose last column
+    tile has 72 columns.  Where N leaves a partial column tile the output is a strided view
+    inside a sentinel-filled buffer: no store past the tile edges."""
     from gvl import _lib
     K_ = _k()
     torch.manual_seed(M + N + K + len(epi) + 7 * b_mn)
@@ -617,6 +620,13 @@ def test_gemm_w4(cuda, b_mn, epi, M, N, K):
         hx = hpre.float().requires_grad_(True)
         O.gelu_erf(hx).sum().backward()
         kw, ref = dict(dact=2, pre_in=hpre.to(cuda)), h * hx.grad
+    big = None
+    if N % 128:  # a partial last column tile: the output inside a sentinel border
+        big = torch.full((M + 3, N + 8), 7.0, dtype=BF, device=cuda)
+        kw["out"] = big[:M, :N]
+        if epi == "res_inplace":
+            kw["out"].copy_(res)
+            kw["residual"] = kw["out"]
     _lib.lib().gvl_gemm_tune(3, 10)
     try:
         name = _kernel_name(A, B, 0, b_mn, M, N, K, epi=epi)
@@ -624,6 +634,8 @@ def test_gemm_w4(cuda, b_mn, epi, M, N, K):
         torch.cuda.synchronize()
     finally:
         _lib.lib().gvl_gemm_tune(3, -1)
+    if big is not None:
+        assert torch.all(big[:, N:] == 7.0) and torch.all(big[M:, :] == 7.0)
     # 128-row tiles (gemm_w4m_kernel / gemm_w4dm_kernel) where 192-row ones would fill < 3/4
     # of the CUs; the direct-A variant where K % 384 == 0 and its epilogue is instantiated
     assert name.startswith(_w4_name(M, K, epi, N, b_mn)), name
@@ -1151,6 +1163,11 @@ def test_cross_entropy(cuda, golden):
     oh[valid, tg[valid]] = 1.0
     want = torch.where(valid.unsqueeze(1), p - oh, torch.zeros_like(p))
     assert rel_err(dl.float().cpu().numpy(), want.numpy()) < 8e-3
+    # per element: max |want| is 1 (the target's p - 1), so the bar above sees almost nothing
+    # of the other 511 columns; every one within a bf16 ulp of softmax - onehot in float64
+    from tests import rowwise_ref as R
+    from tests.helpers import assert_bf16_close
+    assert_bf16_close(dl.cpu(), R.ce_ref64(lg, tg)[1], name="dlogits")
     assert abs(out[1].item() - 1.0 / valid.sum().item()) < 1e-7
     tg2 = torch.from_numpy(fx["ce:targets2"])
     mk = torch.from_numpy(fx["ce:mask"])
@@ -1265,8 +1282,23 @@ def test_pool_clip_full_size(cuda):
 
 # -------------------------------------------------------------------- optimizer path
 def test_grad_norm_and_adamw(cuda, golden):
+    """Two clipped AdamW steps over two groups against the fp32 oracle (max-norm, as before),
+    and per element: every step within one bf16 ulp of a float64 step from the state the
+    kernel read (tests/rowwise_ref.py), p changed wherever that reference's bf16 value changed
+    (near-ties of the rounding aside), and the final p against the reference framework's own
+    result in the fixture (adam:p1_after / adam:p2_after).  The fixture is an fp32 trajectory
+    from the unrounded fp32 p and gradients, so beside assert_bf16_close's one ulp it gets the
+    roundings the bf16 path adds in front: of p going in and after the first step (half an ulp
+    each, in the binade of the larger of old and new p), and of g (twice, 2**-9 each) and the
+    stored m, v (2**-9 each) in the update lr * m^ / sqrt(v^), |m^ / sqrt(v^)| <= 1 on both
+    steps here: 2 steps * lr * (2**-7 + 2**-9 + 2**-10) < 2 * lr * 2**-6.  (An exact float64
+    step rounded to bf16 each time, the best a bf16 path can do, is up to 7.1 ulps from the
+    fixture and more than one ulp off at 196 of p1's 2048 elements.)"""
+    from tests import rowwise_ref as R
+    from tests.helpers import F32_UNIT, assert_bf16_close, f64, ulp_bf16
     K_ = _k()
     fx = golden("ops")
+    base = R.adam_baseline()
     p1 = torch.from_numpy(fx["adam:p1"]).to(BF)
     p2 = torch.from_numpy(fx["adam:p2"]).to(BF)
     g1 = torch.from_numpy(fx["adam:g1"])
@@ -1278,6 +1310,7 @@ def test_grad_norm_and_adamw(cuda, golden):
     refp = [p1.float().clone(), p2.float().clone()]
     st = [(torch.zeros_like(refp[0]), torch.zeros_like(refp[0])),
           (torch.zeros_like(refp[1]), torch.zeros_like(refp[1]))]
+    moved = 0
     for it in range(2):
         gs = [(g1 * (it + 1)).to(BF), (g2 * (it + 1)).to(BF)]
         G = torch.cat([gs[0].reshape(-1), gs[1].reshape(-1)]).to(cuda)
@@ -1285,14 +1318,37 @@ def test_grad_norm_and_adamw(cuda, golden):
         nrm, coef = O.clip_coef([g.float() for g in gs], 1.0)
         assert abs(out[0].item() - float(nrm)) / float(nrm) < 1e-5
         assert abs(out[1].item() - coef) < 1e-6
+        before = dict(p=P.cpu(), m=Mm.cpu(), v=Vv.cpu())
         K_.adamw(P[:n1], G[:n1], Mm[:n1], Vv[:n1], n1, 1e-3, 0.9, 0.95, 1e-8, 0.1, it + 1, out[1:2])
         K_.adamw(P[n1:], G[n1:], Mm[n1:], Vv[n1:], n2, 1e-3, 0.9, 0.95, 1e-8, 0.0, it + 1, out[1:2])
+        after = dict(p=P.cpu(), m=Mm.cpu(), v=Vv.cpu())
+        # one float64 step from what the kernel read (its own clip coefficient included)
+        gsc = R.adam_scaled_grad(G.cpu(), out[1].item())
+        for j, (sl, nd) in enumerate(((slice(0, n1), n1), (slice(n1, n1 + n2), 0))):  # wd 0: no decay
+            ref = R.adamw_ref64(before["p"][sl], gsc[sl], before["m"][sl], before["v"][sl], nd, it + 1)
+            for k in "pmv":
+                assert_bf16_close(after[k][sl], ref[k], scale=ref["scale_" + k], slack=4 * base[k],
+                                  name=f"step {it + 1} group {j} {k}")
+            # p moved wherever the reference's bf16 value did (where fp32 noise cannot flip the
+            # rounding of the reference either way)
+            tie = 4 * base["p"] * F32_UNIT * ref["scale_p"]
+            lo = torch.from_numpy(ref["p"] - tie).to(BF)
+            hi = torch.from_numpy(ref["p"] + tie).to(BF)
+            sure = (lo == hi) & (lo != before["p"][sl])
+            assert sure.any() and bool(torch.all(after["p"][sl][sure] != before["p"][sl][sure]))
+            moved += int(sure.sum())
         for j in range(2):
             O.adamw_update(refp[j], gs[j].float() * coef, st[j][0], st[j][1], it + 1, 1e-3,
                            wd=0.1 if j == 0 else 0.0)
     got = P.float().cpu()
     assert rel_err(got[:n1].numpy(), refp[0].reshape(-1).numpy()) < 1e-2
     assert rel_err(got[n1:].numpy(), refp[1].reshape(-1).numpy()) < 1e-2
+    assert moved >= (n1 + n2) // 2  # of 2 * (n1 + n2) element-steps: the check above had teeth
+    for nm, sl, p0 in (("adam:p1_after", slice(0, n1), p1), ("adam:p2_after", slice(n1, n1 + n2), p2)):
+        want = f64(fx[nm]).reshape(-1)
+        # the docstring's input roundings as an absolute allowance: slack * 2**-24 * scale = extra
+        extra = ulp_bf16(np.maximum(np.abs(want), np.abs(f64(p0).reshape(-1)))) + 2 * 1e-3 * 2.0 ** -6
+        assert_bf16_close(got[sl], want, scale=extra / F32_UNIT, slack=1, name=nm)
 
 
 @pytest.mark.parametrize("rows,cols", [(16384, 768), (8064, 3072), (3, 2304), (0, 16), (777, 264)])
