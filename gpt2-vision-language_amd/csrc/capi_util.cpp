@@ -2,6 +2,8 @@
 #include "capi_util.h"
 #include "../../include/gvl.h"
 
+#include <stdlib.h>
+
 #include <string>
 
 namespace {
@@ -30,6 +32,16 @@ int num_cus() {
     cached[dev] = n;
   }
   return cached[dev];
+}
+
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
 }
 
 bool take_launch_events(hipEvent_t* start, hipEvent_t* stop) {

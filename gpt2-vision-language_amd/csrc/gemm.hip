@@ -155,15 +155,14 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(GemmP p) {
 struct GemmEnv {
   int impl = 3, cfg = -1, group = 0;  // group 0: by shape (gemm_group)
   GemmEnv() {
-    const char* gr = getenv("GVL_GEMM_GROUP");
-    if (gr && atoi(gr) > 0) group = atoi(gr);
+    const int gr = gvl::env_int("GVL_GEMM_GROUP", 0);
+    if (gr > 0) group = gr;
     const char* s = getenv("GVL_GEMM_IMPL");
     if (s && s[0] == 'r' && s[1] == 'e') impl = 0;
     if (s && s[0] == 'l') impl = 1;
     if (s && s[0] == 'r' && s[1] == 'i') impl = 2;
     if (s && s[0] == 'p') impl = 3;
-    const char* c = getenv("GVL_GEMM_CFG");
-    if (c) cfg = atoi(c);
+    cfg = gvl::env_int("GVL_GEMM_CFG", -1);
   }
 };
 GemmEnv& env() {
@@ -237,54 +236,60 @@ extern "C" int gvl_gemm_tune(int32_t impl, int32_t cfg) {
   return 0;
 }
 
+// The routing, once: family by gvl_gemm_tune / GVL_GEMM_IMPL and shape, the family's planner,
+// its launcher down to the leaf, which launches or names its kernel as the sink asks
+// (gemm_common.h).  Returns the family's label for the launch check.
+static const char* gemm_dispatch(const gvl_gemm_desc* d, const gvl::GemmSink& k) {
+  GemmP p;
+  fill_params(d, p);
+  const int impl = env().impl, cfg = env().cfg;
+  if (impl >= 3 && (cfg < 0 || cfg == 12)) {  // AGPR four-wave kernel
+    GemmP q = p;
+    if (gvl::gemm_w4x_plan(q, d->a_mn, d->b_mn, cfg == 12) && gvl::gemm_w4x_launch(q, d->a_mn, d->b_mn, k))
+      return "gvl_gemm(w4x)";
+  }
+  if (impl >= 3 && gvl::gemm_ring_ok(d)) {
+    // cfg 10 forces the four-wave kernel, 3 the persistent one, 13 its in-launch combine;
+    // 11: the default routing without the four-wave kernel
+    GemmP q = p;
+    if (cfg == 10 && gvl::gemm_w4_plan(p, d->a_mn, true)) {
+      gvl::gemm_w4_launch(p, d->b_mn, k);
+    } else if (cfg != 11 && cfg != 13 && cfg != 3 && cfg != 10 && gvl::gemm_w4_plan(p, d->a_mn, false) &&
+               gvl::gemm_w4_launch(p, d->b_mn, k) == 0) {
+    } else if (gvl::gemm_pp3_plan(q, cfg == 3 || cfg == 10)) {
+      gvl::gemm_pp3_launch(q, d->a_mn, d->b_mn, k);
+    } else {
+      gvl::gemm_ring_launch(p, d->a_mn, d->b_mn, gvl::gemm_ring_pick(d->m, d->n, d->k, -1, d->a_mn), k);
+    }
+    return "gvl_gemm(pp)";
+  }
+  if (impl == 2 && gvl::gemm_ring_ok(d)) {
+    gvl::gemm_ring_launch(p, d->a_mn, d->b_mn, gvl::gemm_ring_pick(d->m, d->n, d->k, cfg, d->a_mn), k);
+    return "gvl_gemm(ring)";
+  }
+  if (impl >= 1 && gvl::gemm_lds_ok(d)) {
+    gvl::gemm_lds_launch(p, d->a_mn, d->b_mn, gvl::gemm_lds_pick(d->m, d->n, d->k, cfg > 2 ? -1 : cfg), k);
+    return "gvl_gemm(lds)";
+  }
+  if (gvl::gemm_name_only(k, "gemm_bf16_kernel<%s, %s>", gvl::tf(d->a_mn), gvl::tf(d->b_mn))) return "gvl_gemm";
+  p.tiles_m = (int)((d->m + BM - 1) / BM);
+  p.tiles_n = (int)((d->n + BN - 1) / BN);
+  const dim3 grid(p.tiles_m * p.tiles_n);
+  if (!d->a_mn && !d->b_mn) gvl::launch_timed(gemm_bf16_kernel<false, false>, grid, dim3(NT), 0, k.stream, p);
+  else if (!d->a_mn && d->b_mn) gvl::launch_timed(gemm_bf16_kernel<false, true>, grid, dim3(NT), 0, k.stream, p);
+  else if (d->a_mn && !d->b_mn) gvl::launch_timed(gemm_bf16_kernel<true, false>, grid, dim3(NT), 0, k.stream, p);
+  else gvl::launch_timed(gemm_bf16_kernel<true, true>, grid, dim3(NT), 0, k.stream, p);
+  return "gvl_gemm";
+}
+
+// Name of the kernel instance gvl_gemm(d) launches: the same dispatch with a name-only sink.
 extern "C" int gvl_gemm_kernel_name(const gvl_gemm_desc* d, char* buf, int32_t len) {
   GVL_REQUIRE(d && buf && len > 0, "gvl_gemm_kernel_name: bad arguments");
-  const char* tf[2] = {"false", "true"};
-  if (env().impl >= 3 && (env().cfg < 0 || env().cfg == 12)) {
-    GemmP q;
-    fill_params(d, q);
-    if (gvl::gemm_w4x_plan(q, d->a_mn, d->b_mn, env().cfg == 12)) {
-      snprintf(buf, len, "gemm_w4x_kernel<%d, %d, %s, %s, %d, false>", q.bm, d->a_mn ? q.bn : 192,
-               tf[d->a_mn != 0], tf[d->b_mn != 0], gvl::gemm_epi_kind(q));
-      return 0;
-    }
-  }
-  if (env().impl >= 3 && gvl::gemm_ring_ok(d)) {
-    GemmP p;
-    fill_params(d, p);
-    const int cfg = env().cfg;
-    if ((cfg < 0 || cfg == 10) && gvl::gemm_w4_plan(p, d->a_mn, cfg == 10)) {
-      // (cfg 11: default routing with the four-wave kernel off)
-      const char* epi[EPI_KINDS] = {"0", "1", "2", "3", "4", "5", "6", "7", "8", "9", "10", "11", "12", "13", "14"};
-      if (gvl::gemm_w4d_ok(p))
-        snprintf(buf, len, "%s<%s, %s>", gvl::gemm_w4_rows128(p) ? "gemm_w4dm_kernel" : "gemm_w4d_kernel",
-                 tf[d->b_mn != 0], epi[gvl::gemm_epi_kind(p)]);
-      else
-        snprintf(buf, len, "%s<3, %s, %s>",
-                 gvl::gemm_w4_rows96(p, d->b_mn != 0) ? "gemm_w4r_kernel"
-                 : gvl::gemm_w4_cols96(p, d->b_mn != 0) ? "gemm_w4n_kernel"
-                 : gvl::gemm_w4_rows128(p) ? "gemm_w4m_kernel" : "gemm_w4_kernel",
-                 tf[d->b_mn != 0], epi[gvl::gemm_w4_epi_kind(p)]);
-    } else if (gvl::gemm_pp3_plan(p, cfg == 3 || cfg == 10)) {
-      const char* epi[EPI_KINDS] = {"0", "1", "2", "3", "4", "5", "6", "7", "8", "9", "10", "11", "12", "13", "14"};
-      const bool slab = p.splits > 1 && !(p.splits == 2 && p.tickets);  // partials-only kernel
-      snprintf(buf, len, "gemm_pp3_kernel<4, %s, %s, %s, %d, %d>", tf[d->a_mn != 0], tf[d->b_mn != 0],
-               epi[slab ? 0 : gvl::gemm_epi_kind(p)], p.bn, p.bm);
-    } else {
-      snprintf(buf, len, "%s, %s, %s>", gvl::gemm_ring_name(gvl::gemm_ring_pick(d->m, d->n, d->k, -1, d->a_mn)),
-               tf[d->a_mn != 0], tf[d->b_mn != 0]);
-    }
-  } else if (env().impl == 2 && gvl::gemm_ring_ok(d)) {
-    const int cfg = gvl::gemm_ring_pick(d->m, d->n, d->k, env().cfg, d->a_mn);
-    snprintf(buf, len, "%s, %s, %s>", gvl::gemm_ring_name(cfg), tf[d->a_mn != 0], tf[d->b_mn != 0]);
-  } else if (env().impl >= 1 && gvl::gemm_lds_ok(d)) {
-    const int cfg = gvl::gemm_lds_pick(d->m, d->n, d->k, env().cfg > 2 ? -1 : env().cfg);
-    const int bm[3] = {256, 256, 128}, bn[3] = {256, 128, 128}, wm[3] = {2, 4, 2}, wn[3] = {4, 2, 2};
-    snprintf(buf, len, "gemm_lds_kernel<%d, %d, %d, %d, %s, %s>", bm[cfg], bn[cfg], wm[cfg],
-             wn[cfg], tf[d->a_mn != 0], tf[d->b_mn != 0]);
-  } else {
-    snprintf(buf, len, "gemm_bf16_kernel<%s, %s>", tf[d->a_mn != 0], tf[d->b_mn != 0]);
-  }
+  gvl::GemmSink k;
+  k.launch = false;
+  k.name = buf;
+  k.len = len;
+  gemm_dispatch(d, k);
   return 0;
 }
 
@@ -309,48 +314,9 @@ extern "C" int gvl_gemm(const gvl_gemm_desc* d, gvl_stream_t stream) {
   GVL_REQUIRE(!d->dact || (d->pre_in && d->ldp % 4 == 0), "gvl_gemm: dact needs pre_in");
   GVL_REQUIRE(!d->residual || d->ldr % 4 == 0, "gvl_gemm: ldr must be a multiple of 4");
   GVL_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "gvl_gemm: drop_p out of range");
-  GemmP p;
-  fill_params(d, p);
-  hipStream_t s = gvl::as_stream(stream);
-  if (env().impl >= 3 && (env().cfg < 0 || env().cfg == 12) &&
-      gvl::gemm_w4x_try(p, d->a_mn, d->b_mn, env().cfg == 12, s)) {  // AGPR four-wave kernel
-    GVL_LAUNCH_CHECK("gvl_gemm(w4x)");
-    return 0;
-  }
-  if (env().impl >= 3 && gvl::gemm_ring_ok(d)) {
-    const int cfg = env().cfg;
-    GemmP q = p;
-    if (cfg == 10 && gvl::gemm_w4_plan(p, d->a_mn, true)) {
-      gvl::gemm_w4_launch(p, d->b_mn, s);
-    } else if (cfg != 11 && cfg != 13 && cfg != 3 && cfg != 10 && gvl::gemm_w4_try(p, d->a_mn, d->b_mn, s)) {
-    } else if (gvl::gemm_pp3_plan(q, cfg == 3 || cfg == 10)) {
-      gvl::gemm_pp3_launch(q, d->a_mn, d->b_mn, s);
-    } else {
-      gvl::gemm_ring_launch(p, d->a_mn, d->b_mn, gvl::gemm_ring_pick(d->m, d->n, d->k, -1, d->a_mn), s);
-    }
-    GVL_LAUNCH_CHECK("gvl_gemm(pp)");
-    return 0;
-  }
-  if (env().impl == 2 && gvl::gemm_ring_ok(d)) {
-    const int cfg = gvl::gemm_ring_pick(d->m, d->n, d->k, env().cfg, d->a_mn);
-    gvl::gemm_ring_launch(p, d->a_mn, d->b_mn, cfg, s);
-    GVL_LAUNCH_CHECK("gvl_gemm(ring)");
-    return 0;
-  }
-  if (env().impl >= 1 && gvl::gemm_lds_ok(d)) {
-    const int cfg = gvl::gemm_lds_pick(d->m, d->n, d->k, env().cfg > 2 ? -1 : env().cfg);
-    gvl::gemm_lds_launch(p, d->a_mn, d->b_mn, cfg, s);
-    GVL_LAUNCH_CHECK("gvl_gemm(lds)");
-    return 0;
-  }
-  p.tiles_m = (int)((d->m + BM - 1) / BM);
-  p.tiles_n = (int)((d->n + BN - 1) / BN);
-  const int grid = p.tiles_m * p.tiles_n;
-  if (!d->a_mn && !d->b_mn) gvl::launch_timed(gemm_bf16_kernel<false, false>, dim3(grid), dim3(NT), 0, s, p);
-  else if (!d->a_mn && d->b_mn) gvl::launch_timed(gemm_bf16_kernel<false, true>, dim3(grid), dim3(NT), 0, s, p);
-  else if (d->a_mn && !d->b_mn) gvl::launch_timed(gemm_bf16_kernel<true, false>, dim3(grid), dim3(NT), 0, s, p);
-  else gvl::launch_timed(gemm_bf16_kernel<true, true>, dim3(grid), dim3(NT), 0, s, p);
-  GVL_LAUNCH_CHECK("gvl_gemm");
+  gvl::GemmSink k;
+  k.stream = gvl::as_stream(stream);
+  GVL_LAUNCH_CHECK(gemm_dispatch(d, k));
   return 0;
 }
 
@@ -362,6 +328,15 @@ extern "C" int gvl_gemm(const gvl_gemm_desc* d, gvl_stream_t stream) {
 // anything else, or an unsupported shape, runs the problems one by one through gvl_gemm.
 // name of the kernel instance the last batched call launched ("" after a per-problem fallback)
 static thread_local char g_batched_name[128];
+
+// launches, and keeps the launched instance's name for gvl_gemm_batched_kernel_name
+static gvl::GemmSink batched_sink(gvl_stream_t stream) {
+  gvl::GemmSink k;
+  k.stream = gvl::as_stream(stream);
+  k.name = g_batched_name;
+  k.len = sizeof g_batched_name;
+  return k;
+}
 
 static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t count,
                              gvl_stream_t stream) {
@@ -404,11 +379,9 @@ static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t
     p.Bb[i] = static_cast<const bf16_t*>(d[i].b);
     p.Cb[i] = d[i].c;
   }
-  if (d[0].a_mn && d[0].b_mn && gvl::gemm_w4x_batched_try(p, gvl::as_stream(stream))) {
-    GemmP q = p;
-    gvl::w4x_dw_plan(q);
-    snprintf(g_batched_name, sizeof g_batched_name, "gemm_w4x_kernel<256, %d, true, true, %d, false>",
-             q.bn, gvl::gemm_epi_kind(p));
+  const gvl::GemmSink k = batched_sink(stream);
+  GemmP q = p;
+  if (d[0].a_mn && d[0].b_mn && gvl::w4x_dw_plan(q) && gvl::gemm_w4x_launch(q, 1, 1, k)) {
     GVL_LAUNCH_CHECK("gvl_gemm_batched(w4x)");
     return 0;
   }
@@ -433,10 +406,7 @@ static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t
     // half-K 256 x 256 items.  Estimate as in the planner (gemm_plan.hip): rounds x (32-deep
     // K-steps + 6), a 192-wide step counted 0.75 / 0.9, ~4 for the combine; required >= 10 %
     // better.  GVL_BATCHED_SPLIT=0 turns it off (A/B).
-    static const bool split_on = [] {
-      const char* e = getenv("GVL_BATCHED_SPLIT");
-      return !(e && e[0] == '0');
-    }();
+    static const bool split_on = gvl::env_on("GVL_BATCHED_SPLIT");
     const int64_t tn256 = (p.N + 255) / 256, items2 = 2 * (int64_t)count * tm * tn256;
     const int64_t need = (int64_t)count * 2 * p.M * p.N * 4;
     // a split batch's bias gradients go to gvl_colsum_batched after the GEMM: every one of its
@@ -473,12 +443,7 @@ static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t
     }
     return 0;
   }
-  {
-    const char* tf[2] = {"false", "true"};
-    snprintf(g_batched_name, sizeof g_batched_name, "gemm_pp3_kernel<4, %s, %s, %d, %d, %d>",
-             tf[d[0].a_mn != 0], tf[d[0].b_mn != 0], gvl::gemm_epi_kind(p), p.bn, p.bm);
-  }
-  gvl::gemm_pp3_launch(p, d[0].a_mn, d[0].b_mn, gvl::as_stream(stream));
+  gvl::gemm_pp3_launch(p, d[0].a_mn, d[0].b_mn, k);
   GVL_LAUNCH_CHECK("gvl_gemm_batched");
   if (dbias && p.splits == 2) {  // dbias[i] += column sums of dY_i = A_i stored [K][M]
     const void* xs[GVL_MAX_BATCH];
@@ -537,9 +502,7 @@ extern "C" int gvl_gemm_grouped(const gvl_gemm_desc* d, void* const* dbias, int3
     p.Mb[i] = (int32_t)d[i].m, p.Nb[i] = (int32_t)d[i].n, p.Kb[i] = (int32_t)d[i].k;
     p.ldab[i] = (int32_t)d[i].lda, p.ldbb[i] = (int32_t)d[i].ldb, p.ldcb[i] = (int32_t)d[i].ldc;
   }
-  if (!gvl::gemm_w4x_grouped_try(p, gvl::as_stream(stream))) return -1;
-  snprintf(g_batched_name, sizeof g_batched_name, "gemm_w4x_kernel<256, %d, true, true, %d, true>", p.bn,
-           EPI_RES);
+  if (!gvl::gemm_w4x_grouped_try(p, batched_sink(stream))) return -1;
   GVL_LAUNCH_CHECK("gvl_gemm_grouped");
   return 0;
 }

@@ -1,5 +1,7 @@
 // Shared GEMM parameter block and fused epilogue (gemm.hip, gemm_lds.hip).
 #pragma once
+#include <stdio.h>
+
 #include "common.h"
 #include "../../include/gvl.h"
 
@@ -522,37 +524,48 @@ GVL_DEV void gemm_splitk_gather(const GemmP& p, float4_t (&acc)[FM][FN], int spl
 }
 
 namespace gvl {
-int gemm_lds_pick(int64_t M, int64_t N, int64_t K, int forced);
-int gemm_splitk_pick(int64_t tiles, int64_t K);
-bool gemm_lds_ok(const gvl_gemm_desc* d);
-int gemm_lds_launch(const GemmP& p, int a_mn, int b_mn, int cfg, hipStream_t s);
-void gemm_splitk_reduce_launch(const GemmP& p, hipStream_t s);
-const char* gemm_ring_name(int cfg);
-bool gemm_ring_ok(const gvl_gemm_desc* d);
-int gemm_ring_launch(const GemmP& p, int a_mn, int b_mn, int cfg, hipStream_t s);
-int gemm_ring_pick(int64_t M, int64_t N, int64_t K, int forced, int a_mn);
+// Where a routed GEMM ends up.  Every launcher runs down to the leaf that owns the kernel
+// pointer and hands it a sink: the leaf writes the kernel's name (its own template arguments)
+// when `name` is set, and launches on `stream` when `launch` is set.  gvl_gemm_kernel_name walks
+// the routing with a name-only sink, so the name it reports is the launch's by construction.
+struct GemmSink {
+  hipStream_t stream = nullptr;
+  bool launch = true;
+  char* name = nullptr;
+  int len = 0;
+};
+inline const char* tf(bool b) { return b ? "true" : "false"; }
+// Leaf helper: report the name if asked; true = name only, the leaf returns before it touches
+// the device (no attribute, no launch).
+template <typename... T>
+inline bool gemm_name_only(const GemmSink& k, const char* fmt, T... args) {
+  if (k.name) snprintf(k.name, k.len, fmt, args...);
+  return !k.launch;
+}
+
 int gemm_epi_kind(const GemmP& p);  // EPI_* for the persistent kernels (gemm_plan.hip)
+int gemm_splitk_pick(int64_t tiles, int64_t K);
+void gemm_splitk_reduce_launch(const GemmP& p, hipStream_t s);
+// families: *_ok / *_plan decide, *_launch runs a decided (planned) p down to its leaf
+bool gemm_lds_ok(const gvl_gemm_desc* d);
+int gemm_lds_pick(int64_t M, int64_t N, int64_t K, int forced);
+int gemm_lds_launch(const GemmP& p, int a_mn, int b_mn, int cfg, const GemmSink& k);
+bool gemm_ring_ok(const gvl_gemm_desc* d);
+int gemm_ring_pick(int64_t M, int64_t N, int64_t K, int forced, int a_mn);
+int gemm_ring_launch(const GemmP& p, int a_mn, int b_mn, int cfg, const GemmSink& k);
 bool gemm_pp3_plan(GemmP& p, bool force, int gran = 32);  // gran: K-step depth
-bool gemm_pp3_try(const GemmP& p, int a_mn, int b_mn, hipStream_t s);
 bool pp3_combine_forced();  // gemm.hip: gvl_gemm_tune(3, 13) (the persistent kernel's combine, tests)
-int gemm_pp3_launch(const GemmP& p, int a_mn, int b_mn, hipStream_t s);  // planned p
-int gemm_pp3_launch_ff(const GemmP& p, hipStream_t s);  // gemm_pp3_{ff,ft,tf,tt}.hip
-int gemm_pp3_launch_ft(const GemmP& p, hipStream_t s);
-int gemm_pp3_launch_tf(const GemmP& p, hipStream_t s);
-int gemm_pp3_launch_tt(const GemmP& p, hipStream_t s);
-int gemm_pp3_splits(int64_t M, int64_t N, int64_t K, int gran = 32);
+int gemm_pp3_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& k);
+int gemm_pp3_launch_ff(const GemmP& p, const GemmSink& k);  // gemm_pp3_{ff,ft,tf,tt}.hip
+int gemm_pp3_launch_ft(const GemmP& p, const GemmSink& k);
+int gemm_pp3_launch_tf(const GemmP& p, const GemmSink& k);
+int gemm_pp3_launch_tt(const GemmP& p, const GemmSink& k);
 bool gemm_w4_plan(const GemmP& p, int a_mn, bool force);  // gemm_w4.hip
-int gemm_w4_launch(const GemmP& p, int b_mn, hipStream_t s);
-bool gemm_w4_rows128(const GemmP& p);  // the launch uses 128-row tiles (gemm_w4m_kernel)
-bool gemm_w4_cols96(const GemmP& p, bool b_mn);  // ... and 96-column ones (gemm_w4n_kernel)
-bool gemm_w4_rows96(const GemmP& p, bool b_mn);  // 96 x 128 dX tiles (gemm_w4r_kernel)
-int gemm_w4_epi_kind(const GemmP& p);  // gemm_epi_kind + EPI_GATE_RES (four-wave kernels only)
-bool gemm_w4_try(const GemmP& p, int a_mn, int b_mn, hipStream_t s);
-bool gemm_w4d_ok(const GemmP& p);  // gemm_w4d.hip: direct-A variant for a w4-planned shape
-int gemm_w4d_launch(const GemmP& p, int b_mn, bool rows128, hipStream_t s);
+int gemm_w4_launch(const GemmP& p, int b_mn, const GemmSink& k);  // (also the direct-A variant)
+bool gemm_w4d_ok(const GemmP& p, bool rows128);  // gemm_w4d_f.hip: direct-A variant for a w4-planned shape
+int gemm_w4d_launch(const GemmP& p, int b_mn, bool rows128, const GemmSink& k);
 bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force);  // gemm_w4x.hip: AGPR four-wave kernel
-bool gemm_w4x_try(const GemmP& p, int a_mn, int b_mn, bool force, hipStream_t s);
-bool gemm_w4x_batched_try(const GemmP& p, hipStream_t s);  // batched dW (a_mn, b_mn, C += AB)
-bool w4x_dw_plan(GemmP& p);  // its tile choice (bm / bn / tiles), false when not routed
-bool gemm_w4x_grouped_try(GemmP& p, hipStream_t s);  // grouped dW of different shapes
+bool w4x_dw_plan(GemmP& p);  // batched dW (a_mn, b_mn, C += AB): tile choice, false when not routed
+bool gemm_w4x_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& k);  // false: no instance
+bool gemm_w4x_grouped_try(GemmP& p, const GemmSink& k);  // grouped dW of different shapes
 }  // namespace gvl

@@ -170,7 +170,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(GemmP p) {
 }
 
 template <int BM, int BN, int WMW, int WNW, bool AMN, bool BMN>
-int launch_cfg(const GemmP& p0, hipStream_t s) {
+int launch_cfg(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "gemm_lds_kernel<%d, %d, %d, %d, %s, %s>", BM, BN, WMW, WNW, gvl::tf(AMN),
+                          gvl::tf(BMN)))
+    return 0;
+  hipStream_t s = k.stream;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (int)((p.N + BN - 1) / BN);
@@ -194,7 +198,7 @@ int launch_cfg(const GemmP& p0, hipStream_t s) {
 }
 
 template <bool AMN, bool BMN>
-int launch_layout(const GemmP& p, int cfg, hipStream_t s) {
+int launch_layout(const GemmP& p, int cfg, const gvl::GemmSink& s) {
   switch (cfg) {
     case 0: return launch_cfg<256, 256, 2, 4, AMN, BMN>(p, s);
     case 1: return launch_cfg<256, 128, 4, 2, AMN, BMN>(p, s);
@@ -236,7 +240,7 @@ bool gemm_lds_ok(const gvl_gemm_desc* d) {
          (d->b_mn ? d->k * d->ldb : d->n * d->ldb) * 2 < 0x7fffffffLL;
 }
 
-int gemm_lds_launch(const GemmP& p, int a_mn, int b_mn, int cfg, hipStream_t s) {
+int gemm_lds_launch(const GemmP& p, int a_mn, int b_mn, int cfg, const GemmSink& s) {
   if (!a_mn && !b_mn) return launch_layout<false, false>(p, cfg, s);
   if (!a_mn && b_mn) return launch_layout<false, true>(p, cfg, s);
   if (a_mn && !b_mn) return launch_layout<true, false>(p, cfg, s);

@@ -38,7 +38,7 @@ int gemm_epi_kind(const GemmP& p) {
 // 256x256 tile's 32-deep K-step, T(s) = rounds(tiles*s) * (K/32s + 6) + slab round trip
 // (s fp32 partials written + read, at ~6 TB/s, ~1.1 PF/s of MFMA per 256 CUs); slices must
 // be equal and at least 16 K-steps deep.
-int gemm_pp3_splits(int64_t M, int64_t N, int64_t K, int gran) {
+static int gemm_pp3_splits(int64_t M, int64_t N, int64_t K, int gran) {
   const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
   const int cus = num_cus();
   const double step_s = 2.0 * 256 * 256 * 32 / (1.1e15 / cus);
@@ -70,10 +70,7 @@ static int64_t pp3_min_items() {
 // Output tile width: 192 when its tiles fill the last round of CUs better than 256-wide ones
 // (per-tile efficiency of the narrower tile counted at 0.9); GVL_PP3_BN=256|192 forces one.
 static int pp3_tile_width(int64_t M, int64_t N) {
-  static const int forced = [] {
-    const char* e = getenv("GVL_PP3_BN");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = env_int("GVL_PP3_BN", 0);
   if (N % 64 != 0 || N < 384) return 256;
   if (forced == 256 || forced == 192) return forced;
   const int64_t cus = num_cus(), tm = (M + 255) / 256;
@@ -121,10 +118,7 @@ static void pp3_choose_combined(GemmP& p, int gran) {
 // 128x128 ring at N = 768, 8 % slower than 256x192 at N = 2304); GVL_PP3_BM=128|256
 // forces the height (A/B).
 static int pp3_tile_height(int64_t M, int64_t N, int bn) {
-  static const int forced = [] {
-    const char* e = getenv("GVL_PP3_BM");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = env_int("GVL_PP3_BM", 0);
   static const double e128 = [] {
     const char* e = getenv("GVL_PP3_E128");
     const int v = e ? atoi(e) : 0;
@@ -183,16 +177,10 @@ bool gemm_pp3_plan(GemmP& p, bool force, int gran) {
   return tiles * p.splits >= pp3_min_items();
 }
 
-int gemm_pp3_launch(const GemmP& p, int a_mn, int b_mn, hipStream_t s) {
-  if (!a_mn && !b_mn) return gemm_pp3_launch_ff(p, s);
-  if (!a_mn && b_mn) return gemm_pp3_launch_ft(p, s);
-  if (a_mn && !b_mn) return gemm_pp3_launch_tf(p, s);
-  return gemm_pp3_launch_tt(p, s);
-}
-
-bool gemm_pp3_try(const GemmP& p0, int a_mn, int b_mn, hipStream_t s) {
-  GemmP p = p0;
-  if (!gemm_pp3_plan(p, false)) return false;
-  return gemm_pp3_launch(p, a_mn, b_mn, s) == 0;
+int gemm_pp3_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& k) {
+  if (!a_mn && !b_mn) return gemm_pp3_launch_ff(p, k);
+  if (!a_mn && b_mn) return gemm_pp3_launch_ft(p, k);
+  if (a_mn && !b_mn) return gemm_pp3_launch_tf(p, k);
+  return gemm_pp3_launch_tt(p, k);
 }
 }  // namespace gvl

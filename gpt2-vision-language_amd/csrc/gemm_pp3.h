@@ -416,14 +416,16 @@ __global__ __launch_bounds__(512, 1) void gemm_pp3_kernel(GemmP p) {
 }
 
 template <int NS, bool AMN, bool BMN, int EPI, int BN, int BM>
-int launch_pp3_bn(const GemmP& p0, hipStream_t s) {
-  GemmP p = p0;  // tiles_m/n, splits, kper set by gemm_pp3_try
+int launch_pp3_bn(const GemmP& p0, const gvl::GemmSink& k) {
+  // (for a slab split-K plan this is the kernel named, not the reduce kernel after it)
+  if (gvl::gemm_name_only(k, "gemm_pp3_kernel<%d, %s, %s, %d, %d, %d>", NS, gvl::tf(AMN), gvl::tf(BMN), EPI,
+                          BN, BM))
+    return 0;
+  hipStream_t s = k.stream;
+  GemmP p = p0;  // tiles_m/n, splits, kper set by gemm_pp3_plan
   // counted epilogue (CntEpi): one problem, 32-bit store offsets below the dropped-store offset,
   // a 16-B aligned bias row whose LDS copy fits after the ring (GVL_PP3_CNT=0: off, A/B)
-  static const bool cnt_env = [] {
-    const char* e = getenv("GVL_PP3_CNT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool cnt_env = gvl::env_on("GVL_PP3_CNT");
   constexpr int ring = NS * (BM + BN) * KS * 2;
   const int64_t bias_bytes = EpiKind<EPI>::BIAS ? 2 * (int64_t)p.tiles_n * BN : 0;
   p.cnt = CntEpi<EPI>::ON && cnt_env && p.batch == 1 && ring + bias_bytes <= 160 * 1024 &&
@@ -436,10 +438,7 @@ int launch_pp3_bn(const GemmP& p0, hipStream_t s) {
   // still in the MALL when the CE kernel reads them (Q-Former step 15.21k vs 15.10k images/s
   // with nt); outputs that fit measured far slower (c_fc + GELU 64 -> 120 us in a loop that
   // rewrites them).  profiles/r4/pp3_store_policy_r4n_r4s.txt; GVL_PP3_NT=0 off.
-  static const bool nt_env = [] {
-    const char* e = getenv("GVL_PP3_NT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool nt_env = gvl::env_on("GVL_PP3_NT");
   p.st_nt = p.cnt && nt_env && p.M * p.ldc * 2 > (int64_t)1 << 30;
   const int lds = ring + (p.cnt ? (int)bias_bytes : 0);
   auto kern = gemm_pp3_kernel<NS, AMN, BMN, EPI, BN, BM>;
@@ -467,14 +466,14 @@ int launch_pp3_bn(const GemmP& p0, hipStream_t s) {
 #define GVL_PP3_NS_128 4
 #endif
 template <int NS, bool AMN, bool BMN, int EPI>
-int launch_pp3(const GemmP& p, hipStream_t s) {
+int launch_pp3(const GemmP& p, const gvl::GemmSink& s) {
   if (p.bm == 128) return launch_pp3_bn<GVL_PP3_NS_128, AMN, BMN, EPI, 192, 128>(p, s);
   return p.bn == 192 ? launch_pp3_bn<GVL_PP3_NS_192, AMN, BMN, EPI, 192, 256>(p, s)
                      : launch_pp3_bn<GVL_PP3_NS_256, AMN, BMN, EPI, 256, 256>(p, s);
 }
 
 template <int NS, bool AMN, bool BMN>
-int launch_pp3_epi(const GemmP& p, hipStream_t s) {
+int launch_pp3_epi(const GemmP& p, const gvl::GemmSink& s) {
   // partials only (the reduce kernel applies the epilogue) unless combined in-launch
   if (p.splits > 1 && !(p.splits == 2 && p.tickets)) return launch_pp3<NS, AMN, BMN, EPI_PLAIN>(p, s);
   switch (gvl::gemm_epi_kind(p)) {

@@ -2,5 +2,5 @@
 #include "gemm_pp3.h"
 
 namespace gvl {
-int gemm_pp3_launch_ft(const GemmP& p, hipStream_t s) { return launch_pp3_epi<4, false, true>(p, s); }
+int gemm_pp3_launch_ft(const GemmP& p, const GemmSink& k) { return launch_pp3_epi<4, false, true>(p, k); }
 }  // namespace gvl

@@ -260,7 +260,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
 }
 
 template <int NS, bool AMN, bool BMN>
-int launch_pp(const GemmP& p0, hipStream_t s) {
+int launch_pp(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "gemm_pp_kernel<%d, %s, %s>", NS, gvl::tf(AMN), gvl::tf(BMN))) return 0;
+  hipStream_t s = k.stream;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + 255) / 256);
   p.tiles_n = (int)((p.N + 255) / 256);
@@ -284,7 +286,11 @@ int launch_pp(const GemmP& p0, hipStream_t s) {
 }
 
 template <int BM, int BN, int WMW, int WNW, int NS, int P, bool AMN, bool BMN>
-int launch_cfg(const GemmP& p0, hipStream_t s) {
+int launch_cfg(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "gemm_ring_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", BM, BN, WMW, WNW, NS, P,
+                          gvl::tf(AMN), gvl::tf(BMN)))
+    return 0;
+  hipStream_t s = k.stream;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (int)((p.N + BN - 1) / BN);
@@ -313,7 +319,7 @@ int launch_cfg(const GemmP& p0, hipStream_t s) {
 //      6 = 64x128 (2 waves of 64x64, 4 slots = 48 KiB, three workgroups per CU; needs a
 //          K-contiguous A: the MN-contiguous LDS image is 128 rows wide).
 template <bool AMN, bool BMN>
-int launch_layout(const GemmP& p, int cfg, hipStream_t s) {
+int launch_layout(const GemmP& p, int cfg, const gvl::GemmSink& s) {
   switch (cfg) {
     case 6:
       if constexpr (!AMN) return launch_cfg<64, 128, 1, 2, 4, 1, AMN, BMN>(p, s);
@@ -342,21 +348,6 @@ int launch_layout(const GemmP& p, int cfg, hipStream_t s) {
 }  // namespace
 
 namespace gvl {
-const char* gemm_ring_name(int cfg) {
-  switch (cfg) {
-    case 0: return "gemm_ring_kernel<256, 256, 2, 4, 4, 2";
-    case 1: return "gemm_ring_kernel<256, 128, 4, 2, 5, 1";
-    case 3: return "gemm_ring_kernel<256, 256, 2, 4, 5, 2";
-    case 4: return "gemm_pp_kernel<4";
-    case 5: return "gemm_pp_kernel<5";
-    case 6: return "gemm_ring_kernel<64, 128, 1, 2, 4, 1";
-    case 7: return "gemm_ring_kernel<192, 128, 2, 2, 4, 2";
-    case 8: return "gemm_ring_kernel<192, 256, 2, 2, 4, 2";
-    case 9: return "gemm_ring_kernel<128, 192, 2, 2, 4, 1";
-    default: return "gemm_ring_kernel<128, 128, 2, 2, 4, 1";
-  }
-}
-
 bool gemm_ring_ok(const gvl_gemm_desc* d) {
   return d->k % KS == 0 && d->k > 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
          aligned16(d->a) && aligned16(d->b) &&
@@ -364,7 +355,7 @@ bool gemm_ring_ok(const gvl_gemm_desc* d) {
          (d->b_mn ? d->k * d->ldb : d->n * d->ldb) * 2 < 0x7fffffffLL;
 }
 
-int gemm_ring_launch(const GemmP& p, int a_mn, int b_mn, int cfg, hipStream_t s) {
+int gemm_ring_launch(const GemmP& p, int a_mn, int b_mn, int cfg, const GemmSink& s) {
   if (!a_mn && !b_mn) return launch_layout<false, false>(p, cfg, s);
   if (!a_mn && b_mn) return launch_layout<false, true>(p, cfg, s);
   if (a_mn && !b_mn) return launch_layout<true, false>(p, cfg, s);

@@ -473,10 +473,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4r_kernel(GemmP p) {
 // GVL_W4_GROUP=1 walks all column tiles of a row block before the next one, so an XCD reads
 // each A row block once (and every column block of B); default: the GEMM-wide group.
 int w4_group(int dflt) {
-  static const int g = [] {
-    const char* e = getenv("GVL_W4_GROUP");
-    return e ? atoi(e) : 0;
-  }();
+  static const int g = gvl::env_int("GVL_W4_GROUP", 0);
   return g > 0 ? g : dflt;
 }
 
@@ -488,10 +485,15 @@ constexpr auto w4_kernel_of() {
   else if constexpr (BM == 192) return gemm_w4_kernel<GVL_W4_NS, BMN, EPI>;
   else return gemm_w4m_kernel<GVL_W4_NS, BMN, EPI>;
 }
+template <int BM, int BN>
+constexpr const char* w4_kernel_name() {
+  return BN == 96 ? "gemm_w4n_kernel" : BM == 96 ? "gemm_w4r_kernel" : BM == 192 ? "gemm_w4_kernel" : "gemm_w4m_kernel";
+}
 
 template <bool BMN, int EPI, int BM, int BN = W4_BN>
-int launch_w4_bm(const GemmP& p0, hipStream_t s) {
+int launch_w4_bm(const GemmP& p0, const gvl::GemmSink& k) {
   constexpr int NS = GVL_W4_NS;
+  if (gvl::gemm_name_only(k, "%s<%d, %s, %d>", w4_kernel_name<BM, BN>(), NS, gvl::tf(BMN), EPI)) return 0;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (int)((p.N + BN - 1) / BN);
@@ -508,17 +510,14 @@ int launch_w4_bm(const GemmP& p0, hipStream_t s) {
   }
   const int total = p.tiles_m * p.tiles_n;
   const int grid = total < gvl::num_cus() ? total : gvl::num_cus();
-  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, s, p);
+  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, k.stream, p);
   return 0;
 }
 
 // 128-row tiles where 192-row ones fill under 3/4 of the CUs and 128-row ones fill more
 // (GVL_W4_BM128=0: always 192, A/B)
 bool w4_use128(const GemmP& p) {
-  static const bool on = [] {
-    const char* e = getenv("GVL_W4_BM128");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_W4_BM128");
   const int64_t cus = gvl::num_cus(), tn = (p.N + W4_BN - 1) / W4_BN;
   const int64_t t192 = (p.M + 191) / 192 * tn, t128 = (p.M + 127) / 128 * tn;
   return on && t192 * 4 < cus * 3 && t128 > t192 && t128 <= cus;
@@ -535,10 +534,7 @@ bool w4_use128(const GemmP& p) {
 // (c_fc.dX 35.8 -> 38.5), so only K-contiguous B takes them (GVL_W4_BN96=2: both, A/B).
 // GVL_W4_BN96=0: 128 x 128 as before (A/B).
 bool w4_use96(const GemmP& p, bool b_mn) {
-  static const int mode = [] {
-    const char* e = getenv("GVL_W4_BN96");
-    return e ? atoi(e) : 1;
-  }();
+  static const int mode = gvl::env_int("GVL_W4_BN96", 1);
   if (mode == 0 || (b_mn && mode < 2) || !w4_use128(p)) return false;
   const int64_t cus = gvl::num_cus(), tm = (p.M + 127) / 128;
   const int64_t t128 = tm * ((p.N + 127) / 128), t96 = tm * ((p.N + 95) / 96);
@@ -551,10 +547,7 @@ bool w4_use96(const GemmP& p, bool b_mn) {
 // 256-B rows (the 96-column one of gemm_w4n_kernel lost on dX: 64-B row segments); the A slab is
 // Step96's [96][32] image (two dummy pieces).  GVL_W4_BM96=0: off (A/B).
 bool w4_use96r(const GemmP& p, bool b_mn) {
-  static const bool on = [] {
-    const char* e = getenv("GVL_W4_BM96");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_W4_BM96");
   if (!on || !b_mn || !w4_use128(p)) return false;
   const int64_t cus = gvl::num_cus(), tn = (p.N + 127) / 128;
   const int64_t t128 = (p.M + 127) / 128 * tn, t96 = (p.M + 95) / 96 * tn;
@@ -562,7 +555,7 @@ bool w4_use96r(const GemmP& p, bool b_mn) {
 }
 
 template <bool BMN, int EPI>
-int launch_w4(const GemmP& p, hipStream_t s) {
+int launch_w4(const GemmP& p, const gvl::GemmSink& s) {
   if constexpr (BMN && EPI == EPI_PLAIN) {
     if (w4_use96r(p, BMN)) return launch_w4_bm<BMN, EPI, 96, 128>(p, s);
   }
@@ -570,9 +563,22 @@ int launch_w4(const GemmP& p, hipStream_t s) {
   return w4_use128(p) ? launch_w4_bm<BMN, EPI, 128>(p, s) : launch_w4_bm<BMN, EPI, 192>(p, s);
 }
 
+// The four-wave kernels' epilogue kind: gemm_epi_kind, plus the gated residual (EPI_GATE_RES:
+// bias, residual, gate and the un-gated branch stored to pre_out; no dropout / activation) that
+// every other family runs on the generic epilogue.  Before round 5 the cross-att decoder's 12
+// gated xattn.c_proj GEMMs per step (3968 x 768 x 768) fell to the 128 x 128 ring kernel's
+// runtime-flag epilogue for that reason: 32 us each, 0.058 of peak (VERDICT r4, item 6).
+int w4_epi_kind(const GemmP& p) {
+  static const bool gate_on = gvl::env_on("GVL_W4_GATE");  // =0: the generic path as before (A/B)
+  if (gate_on && p.gate && p.bias && p.residual && p.pre_out && !p.has_drop && !p.c_f32 && !p.act &&
+      !p.dact)
+    return EPI_GATE_RES;
+  return gvl::gemm_epi_kind(p);
+}
+
 template <bool BMN>
-int launch_w4_epi(const GemmP& p, hipStream_t s) {
-  switch (gvl::gemm_w4_epi_kind(p)) {
+int launch_w4_epi(const GemmP& p, const gvl::GemmSink& s) {
+  switch (w4_epi_kind(p)) {
     case EPI_PLAIN: return launch_w4<BMN, EPI_PLAIN>(p, s);
     case EPI_BIAS: return launch_w4<BMN, EPI_BIAS>(p, s);
     case EPI_BIAS_RES: return launch_w4<BMN, EPI_BIAS_RES>(p, s);
@@ -592,10 +598,7 @@ int launch_w4_epi(const GemmP& p, hipStream_t s) {
 
 // Routing: GVL_W4=0 disables, =2 forces it for every shape it supports (tests / A/B).
 int w4_mode() {
-  static const int v = [] {
-    const char* e = getenv("GVL_W4");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = gvl::env_int("GVL_W4", 1);
   return v;
 }
 
@@ -603,28 +606,12 @@ int w4_mode() {
 
 namespace gvl {
 
-// The four-wave kernels' epilogue kind: gemm_epi_kind, plus the gated residual (EPI_GATE_RES:
-// bias, residual, gate and the un-gated branch stored to pre_out; no dropout / activation) that
-// every other family runs on the generic epilogue.  Before round 5 the cross-att decoder's 12
-// gated xattn.c_proj GEMMs per step (3968 x 768 x 768) fell to the 128 x 128 ring kernel's
-// runtime-flag epilogue for that reason: 32 us each, 0.058 of peak (VERDICT r4, item 6).
-int gemm_w4_epi_kind(const GemmP& p) {
-  static const bool gate_on = [] {  // GVL_W4_GATE=0: the generic path as before (A/B)
-    const char* e = getenv("GVL_W4_GATE");
-    return !(e && e[0] == '0');
-  }();
-  if (gate_on && p.gate && p.bias && p.residual && p.pre_out && !p.has_drop && !p.c_f32 && !p.act &&
-      !p.dact)
-    return EPI_GATE_RES;
-  return gemm_epi_kind(p);
-}
-
 // Shapes it takes by default: narrow outputs (N <= 1024) whose 256x256 tiling leaves most CUs
 // idle and whose 192x128 tiling fills at least half the chip.
 bool gemm_w4_plan(const GemmP& p, int a_mn, bool force) {
   if (a_mn || p.c_f32 || p.K % (6 * KS) != 0 || p.N % 8 != 0 || p.ldc % 8 != 0) return false;
   if (p.pre_out && (p.ldp % 8 != 0 || (reinterpret_cast<uintptr_t>(p.pre_out) & 15))) return false;
-  if (gemm_w4_epi_kind(p) == EPI_GEN || gemm_w4_epi_kind(p) == EPI_BIAS_QGELU) return false;
+  if (w4_epi_kind(p) == EPI_GEN || w4_epi_kind(p) == EPI_BIAS_QGELU) return false;
   if (force || w4_mode() == 2) return true;
   if (w4_mode() == 0) return false;
   // GVL_W4=3 (A/B): also the short-K wide outputs (K <= 1024, N <= 4096: c_attn / c_fc
@@ -643,14 +630,8 @@ bool gemm_w4_plan(const GemmP& p, int a_mn, bool force) {
   return tw4 * 5 >= cus * 2 && p.K <= 4096;
 }
 
-bool gemm_w4_rows128(const GemmP& p) { return w4_use128(p); }
-bool gemm_w4_cols96(const GemmP& p, bool b_mn) { return w4_use96(p, b_mn); }
-bool gemm_w4_rows96(const GemmP& p, bool b_mn) {
-  return gemm_w4_epi_kind(p) == EPI_PLAIN && w4_use96r(p, b_mn);
-}
-
-int gemm_w4_launch(const GemmP& p, int b_mn, hipStream_t s) {
-  if (gemm_w4d_ok(p)) {
+int gemm_w4_launch(const GemmP& p, int b_mn, const GemmSink& s) {
+  if (gemm_w4d_ok(p, w4_use128(p))) {
     // direct-A tiles walk all column tiles of a row block before the next one, so an XCD reads
     // each A row block once: HBM bytes per Q-Former dX launch 104 -> 80 MB at equal time
     // (profiles/r3/w4d_group_ab_r3s2.txt); GVL_W4_GROUP overrides
@@ -659,11 +640,6 @@ int gemm_w4_launch(const GemmP& p, int b_mn, hipStream_t s) {
     return gemm_w4d_launch(q, b_mn, w4_use128(q), s);
   }
   return b_mn ? launch_w4_epi<true>(p, s) : launch_w4_epi<false>(p, s);
-}
-
-bool gemm_w4_try(const GemmP& p, int a_mn, int b_mn, hipStream_t s) {
-  if (!gemm_w4_plan(p, a_mn, false)) return false;
-  return gemm_w4_launch(p, b_mn, s) == 0;
 }
 
 }  // namespace gvl

@@ -335,7 +335,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4dm_kernel(GemmP p) {
 }
 
 template <bool BMN, int EPI, int BM>
-int launch_bm(const GemmP& p0, hipStream_t s) {
+int launch_bm(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "%s<%s, %d>", BM == 192 ? "gemm_w4d_kernel" : "gemm_w4dm_kernel", gvl::tf(BMN), EPI))
+    return 0;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + BM - 1) / BM);
   p.tiles_n = (int)((p.N + D_BN - 1) / D_BN);
@@ -345,12 +347,12 @@ int launch_bm(const GemmP& p0, hipStream_t s) {
   auto kern = BM == 192 ? gemm_w4d_kernel<BMN, EPI> : gemm_w4dm_kernel<BMN, EPI>;
   const int total = p.tiles_m * p.tiles_n;
   const int grid = total < gvl::num_cus() ? total : gvl::num_cus();
-  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, s, p);
+  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, k.stream, p);
   return 0;
 }
 
 template <bool BMN, int EPI>
-int launch_rows(const GemmP& p, bool rows128, hipStream_t s) {
+int launch_rows(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
   return rows128 ? launch_bm<BMN, EPI, 128>(p, s) : launch_bm<BMN, EPI, 192>(p, s);
 }
 
@@ -364,7 +366,7 @@ inline bool epi_supported(int e) {
 }
 
 template <bool BMN>
-int launch_epi(const GemmP& p, bool rows128, hipStream_t s) {
+int launch_epi(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
   switch (gvl::gemm_epi_kind(p)) {
     case EPI_PLAIN: return launch_rows<BMN, EPI_PLAIN>(p, rows128, s);
     case EPI_BIAS_RES: return launch_rows<BMN, EPI_BIAS_RES>(p, rows128, s);

@@ -430,22 +430,19 @@ __global__ __launch_bounds__(256, 1) void gemm_w4x_kernel(GemmP p) {
 // CU that frees up, so siblings start within one tile-retire of each other in every round.
 // GVL_W4X_DW_GROUP=n: tile rows per L2 group of the dW tile walk (default: the GEMM's).
 int w4x_np_mode() {
-  static const int v = [] {
-    const char* e = getenv("GVL_W4X_NP");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = gvl::env_int("GVL_W4X_NP", 0);
   return v;
 }
 int w4x_dw_group(int dflt) {
-  static const int v = [] {
-    const char* e = getenv("GVL_W4X_DW_GROUP");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = gvl::env_int("GVL_W4X_DW_GROUP", 0);
   return v > 0 ? v : dflt;
 }
 
 template <int BM, int BN, bool AMN, bool BMN, int EPI, bool GR = false>
-void launch_w4x(const GemmP& p0, hipStream_t s) {
+void launch_w4x(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "gemm_w4x_kernel<%d, %d, %s, %s, %d, %s>", BM, BN, gvl::tf(AMN), gvl::tf(BMN), EPI,
+                          gvl::tf(GR)))
+    return;
   GemmP p = p0;
   constexpr bool DW = AMN && BMN;
   if constexpr (DW) p.group = w4x_dw_group(p.group);
@@ -459,11 +456,11 @@ void launch_w4x(const GemmP& p0, hipStream_t s) {
   const bool np = DW ? w4x_np_mode() >= 1 : w4x_np_mode() >= 2;
   const int grid = (np || total < gvl::num_cus()) ? total : gvl::num_cus();
   constexpr int lds = x_ns<BM>() * (BM + BN) * KS * 2;
-  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, s, p);
+  gvl::launch_timed(kern, dim3(grid), dim3(256), lds, k.stream, p);
 }
 
 template <int BM, bool BMN>
-bool launch_w4x_epi(const GemmP& p, hipStream_t s) {
+bool launch_w4x_epi(const GemmP& p, const gvl::GemmSink& s) {
   switch (gvl::gemm_epi_kind(p)) {
     case EPI_PLAIN: launch_w4x<BM, 192, false, BMN, EPI_PLAIN>(p, s); return true;
     case EPI_BIAS_RES: launch_w4x<BM, 192, false, BMN, EPI_BIAS_RES>(p, s); return true;
@@ -478,18 +475,13 @@ namespace gvl {
 // gvl_gemm_tune(3, 12) forces it too.  LM step 885k -> 900k tokens/s, same box, alternated
 // (profiles/r4/w4x_lm_ab_r4p.txt)
 int w4x_mode() {
-  static const int m = [] {
-    const char* e = getenv("GVL_W4X");
-    return e ? atoi(e) : 1;
-  }();
+  static const int m = env_int("GVL_W4X", 1);
   return m;
 }
 
 // The kernel takes K-contiguous A (activations / dY), either B layout, bf16 out, K % 32 == 0,
 // plain or bias + residual epilogues, one problem, no split.  Routed: outputs whose 256 x 192
 // tiling fills the chip in whole rounds (M = 16384, N = 768: 256 tiles).
-bool w4x_dw_plan(GemmP& p);
-
 bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force) {
   const int epi = gemm_epi_kind(p);
   if (a_mn) return p.batch == 1 && w4x_dw_plan(p) && p.K >= 4096;  // the lm_head's dW (b_mn)
@@ -517,23 +509,23 @@ bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force) {
   // decoder's 8192 rows are 258 of its tiles (a second round for 2 tiles), which sent those
   // GEMMs to the 128 x 128 ring kernel (59-71 us, 30 % of the linear step in r5g) — here they
   // are exactly 256 tiles of 128 x 192
-  static const int rows128 = [] {
-    const char* e = getenv("GVL_W4X_128");
-    return e ? atoi(e) : 2;
-  }();
+  static const int rows128 = env_int("GVL_W4X_128", 2);
   const int64_t t_direct = ((p.M + 191) / 192) * ((p.N + 127) / 128);
   const bool want = rows128 == 1 || (rows128 == 2 && t_direct > cus);
   return want && p.N == 768 && tiles * 10 >= cus * 9 && tiles <= cus;
 }
 
-bool gemm_w4x_dw_try(const GemmP& p0, hipStream_t s);
-
-bool gemm_w4x_try(const GemmP& p0, int a_mn, int b_mn, bool force, hipStream_t s) {
-  GemmP p = p0;
-  if (!gemm_w4x_plan(p, a_mn, b_mn, force)) return false;
-  if (a_mn) return b_mn && gemm_w4x_dw_try(p0, s);
-  if (p.bm == 256) return b_mn ? launch_w4x_epi<256, true>(p, s) : launch_w4x_epi<256, false>(p, s);
-  return b_mn ? launch_w4x_epi<128, true>(p, s) : launch_w4x_epi<128, false>(p, s);
+// p planned by gemm_w4x_plan (one problem) or w4x_dw_plan (a batch of weight gradients).
+// false: the kernel has no instance for it (MN-contiguous A with K-contiguous B), nothing done.
+bool gemm_w4x_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& s) {
+  if (!a_mn) {
+    if (p.bm == 256) return b_mn ? launch_w4x_epi<256, true>(p, s) : launch_w4x_epi<256, false>(p, s);
+    return b_mn ? launch_w4x_epi<128, true>(p, s) : launch_w4x_epi<128, false>(p, s);
+  }
+  if (!b_mn) return false;
+  if (p.bn == 256) launch_w4x<256, 256, true, true, EPI_RES>(p, s);
+  else launch_w4x<256, 192, true, true, EPI_RES>(p, s);
+  return true;
 }
 
 // Weight gradients (dW = dY^T X, both operands MN-contiguous, C += AB): the 12 blocks' of one
@@ -547,10 +539,7 @@ bool gemm_w4x_try(const GemmP& p0, int a_mn, int b_mn, bool force, hipStream_t s
 // attn.c_proj problems (144 / 108 tiles) keep the persistent kernel's in-launch K split.
 // GVL_W4X_DW=0 turns it off (A/B).
 bool w4x_dw_plan(GemmP& p) {
-  static const bool on = [] {
-    const char* e = getenv("GVL_W4X_DW");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("GVL_W4X_DW");
   if (!on || w4x_mode() == 0) return false;
   if (gemm_epi_kind(p) != EPI_RES || p.c_f32 || p.K % KS != 0 || p.K < 2 * KS || p.M % 8 != 0 ||
       p.N % 8 != 0 || p.ldc % 8 != 0 || p.lda % 8 != 0 || p.ldb % 8 != 0)
@@ -569,26 +558,14 @@ bool w4x_dw_plan(GemmP& p) {
   return tiles * 10 >= cus * 9 && (p.bn == 256 ? f256 : f192 / 0.95) >= 0.65;
 }
 
-bool gemm_w4x_dw_try(const GemmP& p0, hipStream_t s) {
-  GemmP p = p0;
-  if (!w4x_dw_plan(p)) return false;
-  if (p.bn == 256) launch_w4x<256, 256, true, true, EPI_RES>(p, s);
-  else launch_w4x<256, 192, true, true, EPI_RES>(p, s);
-  return true;
-}
-bool gemm_w4x_batched_try(const GemmP& p, hipStream_t s) { return gemm_w4x_dw_try(p, s); }
-
 // Weight gradients of different shapes in one launch (gvl_gemm_grouped: the Q-Former bridge's
 // deferred dW of one backward, 2-16 problems of 768 x 768 .. 3072 x 768 at K = 4096 tokens,
 // bias sums fused): whole-K 256 x 256 tiles, the problems' tile lists concatenated (GemmP::gtile);
 // each problem alone would be 9-36 tiles and a split-K launch + reduce + a column-sum pair.
 // Tiles of 256 x 256 or 256 x 192, whichever fills the last round better.
 // p: batch, Ab / Bb / Cb / Db and the per-problem sizes set by the caller.  GVL_W4X_GR=0 off.
-bool gemm_w4x_grouped_try(GemmP& p, hipStream_t s) {
-  static const bool on = [] {
-    const char* e = getenv("GVL_W4X_GR");
-    return !(e && e[0] == '0');
-  }();
+bool gemm_w4x_grouped_try(GemmP& p, const GemmSink& s) {
+  static const bool on = env_on("GVL_W4X_GR");
   if (!on || w4x_mode() == 0 || p.batch < 1 || p.batch > GVL_MAX_GROUP) return false;
   int64_t t192 = 0, t256 = 0;
   for (int i = 0; i < p.batch; ++i) {

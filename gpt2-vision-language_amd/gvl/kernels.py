@@ -78,10 +78,6 @@ def set_kernel_timer(t):
     _timer = t
 
 
-GEMM_NAMES = {(0, 0): "gemm_bf16_kernel<false,false>", (0, 1): "gemm_bf16_kernel<false,true>",
-              (1, 0): "gemm_bf16_kernel<true,false>", (1, 1): "gemm_bf16_kernel<true,true>"}
-
-
 _WS = {}
 GEMM_WORKSPACE_MB = 64
 
@@ -133,28 +129,75 @@ def seed_offset(device):
 
 
 # ------------------------------------------------------------------------------- GEMM
+def _fill_desc(d, who, a, b, out, a_mn, b_mn, out_dtype=None):
+    """Operand checks and the operand fields of GemmDesc d.  out_dtype None: `out` is a given
+    bf16 [M, N] result (batched / grouped); else gemm's, allocated here when None.
+    Returns (out, M, N, K)."""
+    _dev(a, b)
+    _rowmajor(a, "A")
+    _rowmajor(b, "B")
+    given = out_dtype is None
+    if given:
+        _rowmajor(out, "C")
+    if a.dtype != BF16 or b.dtype != BF16 or (given and out.dtype != BF16):
+        raise TypeError(f"gvl.{who}: operands must be bf16")
+    M, K = (a.shape[1], a.shape[0]) if a_mn else (a.shape[0], a.shape[1])
+    N, Kb = (b.shape[1], b.shape[0]) if b_mn else (b.shape[0], b.shape[1])
+    if given:
+        if K != Kb or tuple(out.shape) != (M, N):
+            raise ValueError(f"gvl.{who}: shape mismatch")
+    else:
+        if K != Kb:
+            raise ValueError(f"gvl.{who}: inner dims differ ({K} vs {Kb})")
+        if out is None:
+            out = torch.empty(M, N, dtype=out_dtype, device=a.device)
+        _rowmajor(out, "C")
+    d.a, d.b, d.c = a.data_ptr(), b.data_ptr(), out.data_ptr()
+    d.m, d.n, d.k = M, N, K
+    d.lda, d.ldb, d.ldc = a.stride(0), b.stride(0), out.stride(0)
+    d.a_mn, d.b_mn = int(a_mn), int(b_mn)
+    return out, M, N, K
+
+
+def _batched_name():
+    buf = C.create_string_buffer(128)
+    _L().gvl_gemm_batched_kernel_name(buf, 128)
+    return buf.value.decode()  # "" after a per-problem fallback
+
+
+def _launch(call, name, flops, markers=False):
+    """Runs call() -> True when it launched.  With a KernelTimer set: arms the launch events
+    (dispatch mode; disarmed in `finally`) or, where `markers` allows it, records two stream
+    markers around the call, then appends the record (name(), e0, e1, flops()) of what launched."""
+    if _timer is None or not (_timer.dispatch or markers):
+        return call()
+    dispatch = _timer.dispatch
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    if dispatch:
+        e1.record()  # materialise both hipEvents; the launch re-records them
+        _L().gvl_set_launch_events(C.c_void_p(e0.cuda_event), C.c_void_p(e1.cuda_event))
+    try:
+        ok = call()
+    finally:
+        if dispatch:
+            _L().gvl_set_launch_events(None, None)
+    if not dispatch:
+        e1.record()
+    kernel = name() if ok else ""
+    if kernel:
+        _timer.records.append((kernel, e0, e1, flops()))
+    return ok
+
+
 def gemm(a, b, *, a_mn=False, b_mn=False, out=None, alpha=1.0, alpha_ptr=None, bias=None,
          act=0, dact=0, pre_out=None, pre_in=None, residual=None, gate=None, drop_p=0.0,
          seed=0, seed_ptr=None, out_dtype=BF16):
     """C = epi(alpha * opA @ opB).  a: [M,K] (a_mn=False) or [K,M]; b: [N,K] (b_mn=False,
     nn.Linear weight) or [K,N].  Returns C [M,N]."""
-    _dev(a, b)
-    _rowmajor(a, "A")
-    _rowmajor(b, "B")
-    if a.dtype != BF16 or b.dtype != BF16:
-        raise TypeError("gvl.gemm: operands must be bf16")
-    M, K = (a.shape[1], a.shape[0]) if a_mn else (a.shape[0], a.shape[1])
-    N, Kb = (b.shape[1], b.shape[0]) if b_mn else (b.shape[0], b.shape[1])
-    if K != Kb:
-        raise ValueError(f"gvl.gemm: inner dims differ ({K} vs {Kb})")
-    if out is None:
-        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
-    _rowmajor(out, "C")
     d = GemmDesc()
-    d.a, d.b, d.c = a.data_ptr(), b.data_ptr(), out.data_ptr()
-    d.m, d.n, d.k = M, N, K
-    d.lda, d.ldb, d.ldc = a.stride(0), b.stride(0), out.stride(0)
-    d.a_mn, d.b_mn = int(a_mn), int(b_mn)
+    out, M, N, K = _fill_desc(d, "gemm", a, b, out, a_mn, b_mn, out_dtype)
     d.alpha = float(alpha)
     d.alpha_ptr = _p(alpha_ptr)
     d.bias = _p(bias)
@@ -174,26 +217,17 @@ def gemm(a, b, *, a_mn=False, b_mn=False, out=None, alpha=1.0, alpha_ptr=None, b
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
     tk = _gemm_tickets(a.device)
     d.tickets, d.ticket_count = tk.data_ptr(), tk.numel()
-    if _timer is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        if _timer.dispatch:
-            e0.record()  # materialise both hipEvents; the launch re-records them
-            e1.record()
-            _L().gvl_set_launch_events(C.c_void_p(e0.cuda_event), C.c_void_p(e1.cuda_event))
-            try:
-                _lib.check(_L().gvl_gemm(C.byref(d), _stream()), "gvl_gemm")
-            finally:
-                _L().gvl_set_launch_events(None, None)
-        else:
-            e0.record()
-            _lib.check(_L().gvl_gemm(C.byref(d), _stream()), "gvl_gemm")
-            e1.record()
+
+    def call():
+        _lib.check(_L().gvl_gemm(C.byref(d), _stream()), "gvl_gemm")
+        return True
+
+    def name():
         buf = C.create_string_buffer(128)
         _L().gvl_gemm_kernel_name(C.byref(d), buf, 128)
-        _timer.records.append((buf.value.decode(), e0, e1, 2.0 * M * N * K))
-        return out
-    _lib.check(_L().gvl_gemm(C.byref(d), _stream()), "gvl_gemm")
+        return buf.value.decode()
+
+    _launch(call, name, lambda: 2.0 * M * N * K, markers=True)
     return out
 
 
@@ -225,21 +259,8 @@ def gemm_batched(items, *, a_mn=False, b_mn=False, dbias=None):
     arr = (GemmDesc * n)()
     ws = None
     for i, (a, b, out, acc) in enumerate(items):
-        _dev(a, b)
-        _rowmajor(a, "A")
-        _rowmajor(b, "B")
-        _rowmajor(out, "C")
-        if a.dtype != BF16 or b.dtype != BF16 or out.dtype != BF16:
-            raise TypeError("gvl.gemm_batched: operands must be bf16")
-        M, K_ = (a.shape[1], a.shape[0]) if a_mn else (a.shape[0], a.shape[1])
-        N, Kb = (b.shape[1], b.shape[0]) if b_mn else (b.shape[0], b.shape[1])
-        if K_ != Kb or tuple(out.shape) != (M, N):
-            raise ValueError("gvl.gemm_batched: shape mismatch")
         d = arr[i]
-        d.a, d.b, d.c = a.data_ptr(), b.data_ptr(), out.data_ptr()
-        d.m, d.n, d.k = M, N, K_
-        d.lda, d.ldb, d.ldc = a.stride(0), b.stride(0), out.stride(0)
-        d.a_mn, d.b_mn = int(a_mn), int(b_mn)
+        _fill_desc(d, "gemm_batched", a, b, out, a_mn, b_mn)
         d.alpha = 1.0
         if acc:
             d.residual, d.ldr = out.data_ptr(), out.stride(0)
@@ -249,35 +270,22 @@ def gemm_batched(items, *, a_mn=False, b_mn=False, dbias=None):
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
         if tk is not None:  # the library may split a batch that underfills the chip in two
             d.tickets, d.ticket_count = tk.data_ptr(), tk.numel()
-    ev = None
-    if _timer is not None and _timer.dispatch:  # bound to the batched kernel's own dispatch
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        ev[1].record()
-        _L().gvl_set_launch_events(C.c_void_p(ev[0].cuda_event), C.c_void_p(ev[1].cuda_event))
-    try:
-        if dbias is not None:
-            for t in dbias:
-                if t.dtype != BF16 or not t.is_contiguous():
-                    raise ValueError("gvl.gemm_batched: dbias must be contiguous bf16")
-            da = (C.c_void_p * n)(*[t.data_ptr() for t in dbias])
-            rc = _L().gvl_gemm_batched_dbias(arr, da, n, _stream())
-            if rc not in (0, -1):  # -1: nothing launched, the caller runs the unfused pair
-                _lib.check(rc, "gvl_gemm_batched_dbias")
-            ok = rc == 0
-        else:
+
+    def call():
+        if dbias is None:
             _lib.check(_L().gvl_gemm_batched(arr, n, _stream()), "gvl_gemm_batched")
-            ok = True
-    finally:
-        if ev is not None:
-            _L().gvl_set_launch_events(None, None)
-    if ev is not None and ok:
-        buf = C.create_string_buffer(128)
-        _L().gvl_gemm_batched_kernel_name(buf, 128)
-        if buf.value:  # one batched launch (not the per-problem fallback)
-            flops = sum(2.0 * arr[i].m * arr[i].n * arr[i].k for i in range(n))
-            _timer.records.append((buf.value.decode(), ev[0], ev[1], flops))
-    return ok
+            return True
+        for t in dbias:
+            if t.dtype != BF16 or not t.is_contiguous():
+                raise ValueError("gvl.gemm_batched: dbias must be contiguous bf16")
+        da = (C.c_void_p * n)(*[t.data_ptr() for t in dbias])
+        rc = _L().gvl_gemm_batched_dbias(arr, da, n, _stream())
+        if rc not in (0, -1):  # -1: nothing launched, the caller runs the unfused pair
+            _lib.check(rc, "gvl_gemm_batched_dbias")
+        return rc == 0
+
+    # (timed only by its own dispatch; no record after the per-problem fallback)
+    return _launch(call, _batched_name, lambda: sum(2.0 * d.m * d.n * d.k for d in arr))
 
 
 def gemm_grouped(items, dbias=None):
@@ -296,19 +304,8 @@ def gemm_grouped(items, dbias=None):
         ap = it[3] if len(it) > 3 else None
         if ap is not None and (ap.dtype != torch.float32 or not ap.is_cuda):
             raise TypeError("gvl.gemm_grouped: alpha_ptr must be an fp32 device tensor")
-        _dev(a, b)
-        _rowmajor(a, "A")
-        _rowmajor(b, "B")
-        _rowmajor(out, "C")
-        if a.dtype != BF16 or b.dtype != BF16 or out.dtype != BF16:
-            raise TypeError("gvl.gemm_grouped: operands must be bf16")
-        if a.shape[0] != b.shape[0] or tuple(out.shape) != (a.shape[1], b.shape[1]):
-            raise ValueError("gvl.gemm_grouped: shape mismatch")
         d = arr[i]
-        d.a, d.b, d.c = a.data_ptr(), b.data_ptr(), out.data_ptr()
-        d.m, d.n, d.k = a.shape[1], b.shape[1], a.shape[0]
-        d.lda, d.ldb, d.ldc = a.stride(0), b.stride(0), out.stride(0)
-        d.a_mn, d.b_mn = 1, 1
+        _fill_desc(d, "gemm_grouped", a, b, out, True, True)
         d.alpha = 1.0
         d.alpha_ptr = _p(ap)
         d.residual, d.ldr = out.data_ptr(), out.stride(0)
@@ -318,25 +315,14 @@ def gemm_grouped(items, dbias=None):
             if t is not None and (t.dtype != BF16 or not t.is_contiguous()):
                 raise ValueError("gvl.gemm_grouped: dbias must be contiguous bf16")
         da = (C.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in dbias])
-    ev = None
-    if _timer is not None and _timer.dispatch:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        ev[1].record()
-        _L().gvl_set_launch_events(C.c_void_p(ev[0].cuda_event), C.c_void_p(ev[1].cuda_event))
-    try:
+
+    def call():
         rc = _L().gvl_gemm_grouped(arr, da, n, _stream())
         if rc not in (0, -1):
             _lib.check(rc, "gvl_gemm_grouped")
-    finally:
-        if ev is not None:
-            _L().gvl_set_launch_events(None, None)
-    if rc == 0 and ev is not None:
-        buf = C.create_string_buffer(128)
-        _L().gvl_gemm_batched_kernel_name(buf, 128)
-        flops = sum(2.0 * arr[i].m * arr[i].n * arr[i].k for i in range(n))
-        _timer.records.append((buf.value.decode(), ev[0], ev[1], flops))
-    return rc == 0
+        return rc == 0
+
+    return _launch(call, _batched_name, lambda: sum(2.0 * d.m * d.n * d.k for d in arr))
 
 
 # ------------------------------------------------------------------------- LayerNorm

@@ -758,6 +758,49 @@ def test_gemm_ring_band(cuda, a_mn, b_mn, epi, M, N, K, cfg):
     assert rel_err(y.float().cpu().numpy(), ref.detach().numpy()) < 8e-3
 
 
+@pytest.mark.parametrize("M,N,K,a_mn,b_mn,epi,tune", [
+    (7680, 2048, 4096, 1, 0, "res_inplace", (3, -1)),  # once named gemm_w4x_kernel: no such instance
+    (3456, 768, 768, 0, 0, "bias", (3, 12)),           # once named gemm_ring_kernel: the w4 family takes it
+    (256, 256, 256, 1, 1, "plain", (2, 7))])           # once named 192 x 128: MN-contiguous A falls back
+def test_gemm_once_misnamed_routes(cuda, M, N, K, a_mn, b_mn, epi, tune):
+    """The three routes whose reported name differed from the launch before the name query moved
+    onto the dispatch (tests/data/gemm_routes.json, "was"): the GEMM runs once under its setting,
+    vs the fp32 product, and the name is the table's."""
+    import json
+    K_ = _k()
+    from gvl import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    table = json.load(open(os.path.join(root, "tests", "data", "gemm_routes.json")))
+    row = next(r for r in table["rows"]
+               if (r["m"], r["n"], r["k"], r["a_mn"], r["b_mn"], r["epi"]) == (M, N, K, a_mn, b_mn, epi))
+    cell = "%d:%d" % tune
+    want = table["names"][row["ws"][table["settings"].index(cell)]]
+    assert cell + "/ws" in row["was"] and row["was"][cell + "/ws"] != want
+    torch.manual_seed(M + N + K)
+    a = torch.randn(M, K).to(BF)
+    b = (torch.randn(K, N) * 0.05).to(BF)
+    A = (a.t().contiguous() if a_mn else a).to(cuda)
+    B = (b if b_mn else b.t().contiguous()).to(cuda)
+    ref = a.float() @ b.float()
+    kw = {}
+    if epi == "bias":
+        bias = torch.randn(N).to(BF)
+        kw, ref = dict(bias=bias.to(cuda)), ref + bias.float()
+    elif epi == "res_inplace":
+        c0 = torch.randn(M, N).to(BF)
+        acc = c0.to(cuda)
+        kw, ref = dict(residual=acc, out=acc), ref + c0.float()
+    _lib.lib().gvl_gemm_tune(*tune)
+    try:
+        name = _kernel_name(A, B, a_mn, b_mn, M, N, K, epi=epi)
+        y = K_.gemm(A, B, a_mn=bool(a_mn), b_mn=bool(b_mn), **kw)
+        torch.cuda.synchronize()
+    finally:
+        _lib.lib().gvl_gemm_tune(3, -1)
+    assert name == want, (name, want)
+    assert rel_err(y.float().cpu().numpy(), ref.numpy()) < 8e-3
+
+
 @pytest.mark.parametrize("act", [1, 2])
 def test_gemm_epilogue_act_bias_residual(cuda, act):
     K_ = _k()
