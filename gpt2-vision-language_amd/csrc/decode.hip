@@ -5,6 +5,8 @@
 // cached key against the new query (one key per thread, 8 x 16-B loads of its 64-dim row) into
 // an LDS score array, block max/sum in fp32; pass 2 accumulates p_t * v_t with 8 threads per
 // value row (16-B loads, 32 rows in flight per sweep) and folds the 32 partial rows in LDS.
+// Its IND instance (gvl_attn_decode_beam, beam search) takes the cache row of every key / value
+// from an int32 table src[sequence][position]; the plain instance is unchanged by it.
 //
 // sample_kernel: one 1024-thread workgroup per row; the row (V <= 65536) sits in registers as
 // contiguous 64-element chunks.  softmax(logits / T) -> top-k by an 8-bit radix select on the
@@ -29,8 +31,13 @@ struct DecP {
   bf16_t* o;
   int64_t Tk, q_sb, k_sb, k_st, v_sb, v_st, o_sb;
   float scale;
+  const int32_t* src;  // IND: physical cache row of (sequence, position)
+  int64_t src_ld;
 };
 
+// IND (gvl_attn_decode_beam): the key / value of position t of sequence b come from cache row
+// src[b][t] instead of row b; everything else, the order of accumulation included, is shared.
+template <bool IND>
 __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   __shared__ float qs[64];
   __shared__ float sc[DEC_MAXT];
@@ -42,10 +49,13 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   float q[64];
 #pragma unroll
   for (int d = 0; d < 64; ++d) q[d] = qs[d];
-  const bf16_t* kb = p.k + b * p.k_sb + h * 64;
+  const bf16_t* kb = p.k + (IND ? 0 : b * p.k_sb) + h * 64;
+  const int32_t* srow = IND ? p.src + b * p.src_ld : nullptr;
+  const int rmax = (int)gridDim.y - 1;
   float mx = -INFINITY;
   for (int64_t t = tid; t < p.Tk; t += DEC_NT) {
-    const uint4* row = reinterpret_cast<const uint4*>(kb + t * p.k_st);
+    const int64_t kr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.k_sb : 0;
+    const uint4* row = reinterpret_cast<const uint4*>(kb + kr + t * p.k_st);
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -66,11 +76,12 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   }
   l = block_sum<DEC_NT>(l, red);  // (its barriers also publish sc[])
   const int d8 = tid & 7, tg = tid >> 3;
-  const bf16_t* vb = p.v + b * p.v_sb + h * 64 + d8 * 8;
+  const bf16_t* vb = p.v + (IND ? 0 : b * p.v_sb) + h * 64 + d8 * 8;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int64_t t = tg; t < p.Tk; t += 32) {
+    const int64_t vr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.v_sb : 0;
     float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(vb + t * p.v_st), f);
+    unpack8(*reinterpret_cast<const uint4*>(vb + vr + t * p.v_st), f);
     const float w = sc[t];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = fmaf(w, f[j], acc[j]);
@@ -304,10 +315,36 @@ extern "C" int gvl_attn_decode(const void* q, int64_t q_sb, const void* k, int64
   if (B == 0 || H == 0) return 0;
   DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
          static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
-         v_sb, v_st, o_sb, scale};
-  hipLaunchKernelGGL(attn_decode_kernel, dim3((unsigned)H, (unsigned)B), dim3(DEC_NT), 0,
+         v_sb, v_st, o_sb, scale, nullptr, 0};
+  hipLaunchKernelGGL(attn_decode_kernel<false>, dim3((unsigned)H, (unsigned)B), dim3(DEC_NT), 0,
                      gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_attn_decode");
+  return 0;
+}
+
+extern "C" int gvl_attn_decode_beam(const void* q, int64_t q_sb, const void* k, int64_t k_sb,
+                                    int64_t k_st, const void* v, int64_t v_sb, int64_t v_st,
+                                    void* o, int64_t o_sb, int64_t B, int64_t H, int64_t Tk,
+                                    float scale, const int32_t* src, int64_t src_ld,
+                                    gvl_stream_t stream) {
+  GVL_REQUIRE(q && k && v && o, "gvl_attn_decode_beam: null buffer");
+  GVL_REQUIRE(src, "gvl_attn_decode_beam: null src table");
+  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "gvl_attn_decode_beam: Tk=%lld out of range (1..%d)",
+              (long long)Tk, DEC_MAXT);
+  GVL_REQUIRE(src_ld >= Tk, "gvl_attn_decode_beam: src_ld=%lld < Tk=%lld", (long long)src_ld,
+              (long long)Tk);
+  GVL_REQUIRE(B >= 0 && B <= 65535 && H >= 0, "gvl_attn_decode_beam: B=%lld / H=%lld out of range",
+              (long long)B, (long long)H);
+  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
+                  gvl::aligned16(k) && gvl::aligned16(v),
+              "gvl_attn_decode_beam: K/V rows must be 16-byte aligned");
+  if (B == 0 || H == 0) return 0;
+  DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
+         static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
+         v_sb, v_st, o_sb, scale, src, src_ld};
+  hipLaunchKernelGGL(attn_decode_kernel<true>, dim3((unsigned)H, (unsigned)B), dim3(DEC_NT), 0,
+                     gvl::as_stream(stream), p);
+  GVL_LAUNCH_CHECK("gvl_attn_decode_beam");
   return 0;
 }
 

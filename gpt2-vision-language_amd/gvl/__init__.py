@@ -6,7 +6,8 @@ Drop-in module APIs:
     gvl.cross_att  -> source/gpt2_cross-att/model.py
 Runtime:
     gvl.optim (fused AdamW + clip), gvl.dist (bucketed RCCL all-reduce), gvl.train (the
-    grad-accumulation DP step), gvl.generate (greedy decode), gvl.kernels (C-ABI wrappers).
+    grad-accumulation DP step), gvl.generate (greedy decode), gvl.decode (KV-cached sampling and
+    beam search; gvl.beam_search is gvl.decode.beam_search), gvl.kernels (C-ABI wrappers).
 All compute goes through libgvl.so (include/gvl.h); importing a module that needs it on a
 machine without the built library raises at first use, there is no fallback.
 """
@@ -14,6 +15,18 @@ import os as _os
 
 __version__ = "0.1.0"
 PACKAGE_DIR = _os.path.dirname(_os.path.abspath(__file__))
+
+
+# KV-cached decoding (gvl.decode), resolved on first use so that `import gvl` stays light.
+# (decode.generate is not re-exported: gvl.generate is the full-recompute greedy module.)
+_DECODE_NAMES = ("beam_search", "KVDecoder", "BeamDecoder")
+
+
+def __getattr__(name):
+    if name in _DECODE_NAMES:
+        from . import decode
+        return getattr(decode, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def library_path():

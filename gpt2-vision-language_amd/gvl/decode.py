@@ -13,7 +13,11 @@ token costs one row through each block:
     layer's kv_proj(z_proj) (gpt2_cross-att/model.py:160-165, :49-57);
   * the next token comes from gvl_sample (temperature / top-k / top-p, inverse CDF of a
     uniform drawn from the caller's torch.Generator) or its greedy form (top_k = 1, u = 0:
-    the first maximum, torch.argmax's tie-break).
+    the first maximum, torch.argmax's tie-break);
+  * beam search (BeamDecoder, beam_search): B items x K beams share one R = B*K-row cache
+    through an int32 indirection table src[r, t] (the row holding position t of hypothesis r),
+    so reordering beams rewrites the table (gvl_beam_step) and attention reads through it
+    (gvl_attn_decode_beam); the prefix is prefilled once per item and no cache row is copied.
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
@@ -62,6 +66,7 @@ class KVDecoder:
         self.block_size = dec.config.block_size
         C = self.wte.shape[1]
         self.C, self.B, self.max_new = C, batch, max_new
+        self.rows = batch  # sequences per step() (BeamDecoder: batch * beams)
         self.Tmax = 0
         self.cache = None  # allocated by prefill: [B, prefix + max_new, 3C] per layer
         self.kvz = None
@@ -79,11 +84,20 @@ class KVDecoder:
         q = K.linear(self._ln(x2, P["ln"]), *P["q"])
         C = self.C
         if S == 1:
-            y = K.attn_decode(q, kvz[:, :, :C], kvz[:, :, C:], P["H"])
+            y = self._attend(q, kvz[:, :, :C], kvz[:, :, C:], P["H"], True)
         else:
             y = K.attn_fwd(q.view(self.B, S, C), kvz[:, :, :C], kvz[:, :, C:], P["H"], False)[0]
             y = y.view(self.B * S, C)
         return K.linear(y, P["c"][0], P["c"][1], residual=x2, gate=P["gate"])
+
+    def _attend(self, q, k, v, H, cross):
+        """One new query per row over cached keys / values (self-attention cache, or the
+        cross-att model's projected image tokens)."""
+        return K.attn_decode(q, k, v, H)
+
+    def _alloc_cache(self, B, C, device):
+        """Per-layer [B, Tmax, 3C] cache tensors the prefill writes."""
+        return [torch.empty(B, self.Tmax, 3 * C, dtype=BF16, device=device) for _ in self.blocks]
 
     def _mlp(self, x2, P):
         h = K.linear(self._ln(x2, P["ln2"]), *P["fc"], act=1)
@@ -102,8 +116,7 @@ class KVDecoder:
         logits of the last position [B, V]."""
         B, S, C = x_emb.shape
         self.Tmax = S + self.max_new
-        self.cache = [torch.empty(B, self.Tmax, 3 * C, dtype=BF16, device=x_emb.device)
-                      for _ in self.blocks]
+        self.cache = self._alloc_cache(B, C, x_emb.device)
         x2 = x_emb.to(BF16).reshape(B * S, C).contiguous()
         for l, P in enumerate(self.blocks):
             if self.cross is not None:
@@ -121,7 +134,7 @@ class KVDecoder:
     @torch.no_grad()
     def step(self, ids):
         """Append one token per sequence (ids [B]) and return the next logits [B, V]."""
-        B, C, t = self.B, self.C, self.t
+        B, C, t = self.rows, self.C, self.t
         if t >= self.Tmax:
             raise ValueError("KV cache full")
         pos = t - self.txt0
@@ -137,7 +150,7 @@ class KVDecoder:
             row = self.cache[l][:, t]  # [B, 3C] view, row stride Tmax*3C
             K.linear(self._ln(x2, P["ln1"]), *P["attn"], out=row)
             cl = self.cache[l][:, :t + 1]
-            y = K.attn_decode(row[:, :C], cl[:, :, C:2 * C], cl[:, :, 2 * C:], P["H"])
+            y = self._attend(row[:, :C], cl[:, :, C:2 * C], cl[:, :, 2 * C:], P["H"], False)
             x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
             x2 = self._mlp(x2, P)
         self.t = t + 1
@@ -171,6 +184,76 @@ class KVDecoder:
         return self.prefill(emb)
 
 
+class BeamDecoder(KVDecoder):
+    """KVDecoder for beam search: B items x K beams = R cache rows, and an int32 table
+    src [R, Tmax] naming, per hypothesis and position, the cache row that holds its key / value.
+
+    The prefix is prefilled once per item, at batch B, into cache rows b*K (src[:, :t0] = b*K);
+    step(ids, src) appends one token per hypothesis into the hypothesis' own row and attends
+    through src (gvl_attn_decode_beam), so reordering beams rewrites the table, never the cache.
+    The cross-att model's kv_proj(z_proj) stays at B rows, read through a constant table.
+    cache_fill: a value to fill the new cache with (a test hook: rows the prefill must not
+    write keep it)."""
+
+    def __init__(self, model, batch: int, beams: int, max_new: int, cache_fill=None):
+        super().__init__(model, batch, max_new)
+        if not 1 <= beams <= 8:
+            raise ValueError(f"beams={beams}: 1..8 supported")
+        self.K = beams
+        self.rows = batch * beams
+        self.cache_fill = cache_fill
+        self.prefill_batch = None
+        self.src = None
+        self.kv_src = None
+
+    def _alloc_cache(self, B, C, device):
+        self._full = [torch.empty(B * self.K, self.Tmax, 3 * C, dtype=BF16, device=device)
+                      for _ in self.blocks]
+        if self.cache_fill is not None:
+            for c in self._full:
+                c.fill_(self.cache_fill)
+        return [c.view(B, self.K, self.Tmax, 3 * C)[:, 0] for c in self._full]  # rows b*K
+
+    def _attend(self, q, k, v, H, cross):
+        if self.src is None:  # a one-token prefill of the cross-att model: B plain rows
+            return super()._attend(q, k, v, H, cross)
+        return K.attn_decode_beam(q, k, v, H, self.kv_src if cross else self.src)
+
+    @torch.no_grad()
+    def prefill(self, x_emb):
+        self.prefill_batch = x_emb.shape[0]
+        logits = super().prefill(x_emb)
+        self.cache, self._full = self._full, None  # step() sees all R rows
+        return logits
+
+    @torch.no_grad()
+    def start(self, prompt_ids, z=None):
+        """Prefill at batch B.  Returns the items' logits [B, V] (those of slot 0 of each)."""
+        logits = super().start(prompt_ids, z)
+        if self.kvz is not None:
+            Sz = self.kvz[0].shape[1]
+            item = torch.arange(self.rows, device=logits.device, dtype=torch.int32) // self.K
+            self.kv_src = item.view(-1, 1).expand(self.rows, Sz).contiguous()
+        return logits
+
+    def initial_src(self, device):
+        """src [R, Tmax] with the prefix columns pointing at the items' prefilled rows b*K."""
+        src = torch.zeros(self.rows, self.Tmax, dtype=torch.int32, device=device)
+        first = torch.arange(self.rows, device=device, dtype=torch.int32) // self.K * self.K
+        src[:, :self.t] = first.view(-1, 1)
+        return src
+
+    @torch.no_grad()
+    def step(self, ids, src):
+        """Append one token per hypothesis (ids [R]) whose cached positions are src[r, :t]
+        (src[r, t] = r: the new token lands in its own row).  Returns the next logits [R, V]."""
+        self.src = src
+        try:
+            return super().step(ids)
+        finally:
+            self.src = None
+
+
 def sample_next(logits, *, greedy=False, temperature=1.0, top_k=0, top_p=1.0, generator=None):
     """Next token ids [B] from logits [B, V] on the gvl_sample kernel."""
     rows = logits.shape[0]
@@ -201,3 +284,56 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
             logits = dec.step(nxt)
     ids = torch.stack(out, dim=1)
     return (ids, torch.stack(lg, dim=1)) if return_logits else ids
+
+
+@torch.no_grad()
+def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
+                return_all=False):
+    """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
+    hypotheses per item.  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
+    tokens; hypotheses are ranked by raw * n ** -length_penalty (n = its length, end token
+    included), ties to the lower parent slot and then the lower token id (gvl_beam_step).  One
+    that emits `eos` is finished and competes with its final score; the search ends after n_new
+    steps or once every hypothesis is finished (eos=None: never).
+    Returns (ids [B, n_new] of the best hypothesis, padded with eos past its end, lengths [B],
+    raw scores [B]); return_all: all of them in rank order, [B, K, n_new], [B, K], [B, K]."""
+    B, Kb = prompt_ids.shape[0], num_beams
+    R = B * Kb
+    dec = BeamDecoder(model, B, Kb, n_new)
+    first = dec.start(prompt_ids, z)
+    dev, V, t0 = first.device, first.shape[1], dec.t
+    logits = torch.empty(R, V, dtype=first.dtype, device=dev)
+    logits.view(B, Kb, V)[:, 0] = first  # slots 1.. start empty (score -inf): never read
+    len_norm = torch.arange(n_new + 2, dtype=torch.float32).clamp_(min=1.0).pow_(
+        -float(length_penalty)).to(dev)
+    score = torch.full((B, Kb), float("-inf"), dtype=torch.float32, device=dev)
+    score[:, 0] = 0.0
+    score = [score.view(R), torch.empty(R, dtype=torch.float32, device=dev)]
+    flen = [torch.zeros(R, dtype=torch.int32, device=dev) for _ in range(2)]
+    src = [dec.initial_src(dev), torch.zeros(R, dec.Tmax, dtype=torch.int32, device=dev)]
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    nws = K._L().gvl_beam_step_workspace_size(B, Kb)
+    ws = torch.empty(max(nws, 8) // 4, dtype=torch.float32, device=dev)
+    toks, cur = [], 0
+    for s in range(n_new):
+        tok = torch.empty(R, dtype=torch.int64, device=dev)
+        K.beam_step(logits, score[cur], flen[cur], len_norm, src[cur], Kb, s, eos, t0,
+                    out=(tok, parent, score[1 - cur], flen[1 - cur], src[1 - cur]), workspace=ws)
+        cur = 1 - cur
+        toks.append(tok)
+        if s + 1 == n_new:
+            break
+        # finished hypotheses only carry over, in their order: stopping here or later is the same
+        if eos is not None and bool(((flen[cur] > 0) | (score[cur] == float("-inf"))).all()):
+            break
+        logits = dec.step(tok, src[cur])
+    S = len(toks)
+    ids = torch.stack(toks, dim=1).gather(0, src[cur][:, t0:t0 + S].long())
+    if S < n_new:
+        ids = torch.cat([ids, ids.new_full((R, n_new - S), eos)], dim=1)
+    live = torch.where(score[cur] == float("-inf"), 0, S).to(torch.int32)
+    lengths = torch.where(flen[cur] > 0, flen[cur], live)
+    ids, lengths, scores = ids.view(B, Kb, n_new), lengths.view(B, Kb), score[cur].view(B, Kb)
+    if return_all:
+        return ids, lengths, scores.clone()
+    return ids[:, 0], lengths[:, 0], scores[:, 0].clone()

@@ -464,6 +464,71 @@ def attn_decode(q, k, v, H, out=None, scale=None):
     return out
 
 
+def attn_decode_beam(q, k, v, H, src, out=None, scale=None):
+    """attn_decode with cache indirection (include/gvl.h gvl_attn_decode_beam): sequence r
+    reads position t from cache row src[r, t].  q [R, *]; k/v [rows, Tk, *] strided views of the
+    physical cache; src int32 [R, >= Tk] with entries in [0, R).  -> o [R, H*64]."""
+    _dev(q, k, v, src)
+    _rowmajor(src, "src")
+    if src.dtype != torch.int32 or src.shape[0] != q.shape[0]:
+        raise ValueError("gvl: src must be an int32 [rows of q, >= Tk] table")
+    R, Tk = q.shape[0], k.shape[1]
+    if k.shape[0] > R or v.shape[0] > R:
+        raise ValueError("gvl: the cache has more rows than q; src could not name them")
+    if out is None:
+        out = torch.empty(R, H * 64, dtype=BF16, device=q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(64)
+    _lib.check(_L().gvl_attn_decode_beam(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
+                                         k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
+                                         out.data_ptr(), out.stride(0), R, H, Tk, float(scale),
+                                         src.data_ptr(), src.stride(0), _stream()),
+               "gvl_attn_decode_beam")
+    return out
+
+
+def beam_step(logits2, score, flen, len_norm, src, K, step, eos, t0, out=None, workspace=None):
+    """One beam-search step for B items x K beams (include/gvl.h gvl_beam_step).  logits2
+    [B*K, V] bf16 / fp32; score fp32 [B*K]; flen int32 [B*K]; len_norm fp32 [>= step + 2]; src
+    int32 [B*K, > t0 + step]; eos None or -1: no end token.  out: (tok int64, parent int32,
+    score fp32, flen int32, src int32) to write instead of new tensors; src of `out` must not be
+    the input table.  -> that tuple."""
+    _dev(logits2, score, flen, len_norm, src)
+    _rowmajor(logits2, "logits")
+    _rowmajor(src, "src")
+    R, V = logits2.shape
+    if K < 1 or R % K:
+        raise ValueError(f"gvl: {R} logits rows are not B x K = {K} beams")
+    if (score.dtype != F32 or flen.dtype != torch.int32 or len_norm.dtype != F32 or
+            src.dtype != torch.int32 or logits2.dtype not in (BF16, F32)):
+        raise ValueError("gvl: beam_step takes fp32 score / len_norm, int32 flen / src and bf16 "
+                         "or fp32 logits")
+    if score.numel() != R or flen.numel() != R or src.shape[0] != R or len_norm.numel() < step + 2:
+        raise ValueError("gvl: beam_step state does not match the logits rows / step")
+    dev = logits2.device
+    if out is None:
+        out = (torch.empty(R, dtype=torch.int64, device=dev),
+               torch.empty(R, dtype=torch.int32, device=dev),
+               torch.empty(R, dtype=F32, device=dev),
+               torch.empty(R, dtype=torch.int32, device=dev), torch.empty_like(src))
+    tok, parent, score_o, flen_o, src_o = out
+    if src_o.shape != src.shape or src_o.stride() != src.stride():
+        raise ValueError("gvl: the output src table must have the input table's layout")
+    nws = _L().gvl_beam_step_workspace_size(R // K, K)
+    if workspace is None:
+        workspace = torch.empty(max(nws, 8) // 4, dtype=F32, device=dev)
+    elif workspace.numel() * workspace.element_size() < nws:
+        raise ValueError(f"gvl: beam_step workspace needs {nws} bytes")
+    _lib.check(_L().gvl_beam_step(logits2.data_ptr(), logits2.stride(0), int(logits2.dtype == F32),
+                                  R // K, K, V, score.data_ptr(), flen.data_ptr(),
+                                  len_norm.data_ptr(), int(step), -1 if eos is None else int(eos),
+                                  int(t0), src.data_ptr(), src.stride(0), tok.data_ptr(),
+                                  parent.data_ptr(), score_o.data_ptr(), flen_o.data_ptr(),
+                                  src_o.data_ptr(), workspace.data_ptr(), _stream()),
+               "gvl_beam_step")
+    return out
+
+
 def sample(logits2, u, temperature=1.0, top_k=0, top_p=1.0, out=None):
     """Fused temperature / top-k / top-p draw per row (include/gvl.h gvl_sample); u [rows]
     fp32 uniforms in [0, 1) on the device.  -> int64 [rows]."""

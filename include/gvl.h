@@ -343,6 +343,47 @@ int gvl_sample(const void* logits, int64_t ld, int32_t logits_fp32, int64_t rows
                float temperature, int32_t top_k, float top_p, const float* u, int64_t* out,
                gvl_stream_t stream);
 
+/* Beam-search decoding.  Added at ABI v14 without a version bump: both entry points are new
+ * symbols and nothing existing changes, so a v14 caller keeps working against this library.
+ *
+ * gvl_attn_decode_beam: gvl_attn_decode with cache indirection.  Sequence r reads cached
+ * position t from physical cache row src[r*src_ld + t] (int32, each in [0, B); the kernel
+ * clamps an entry outside that range so a bad table cannot read outside the cache): its key is
+ * at k + row*k_sb + t*k_st + h*64, likewise v.  q and o are indexed by r as before.  Same
+ * limits (Tk <= 4096, 16-byte-aligned rows), arithmetic and accumulation order as
+ * gvl_attn_decode: on a cache gathered by src the two give the same bits.  A beam step only
+ * rewrites the small src table instead of copying reordered cache rows.
+ *
+ * gvl_beam_step: one beam-search step for B items x K beams (1 <= K <= 8, K <= V <= 65536),
+ * row r = b*K + j.  logits [B*K, V] bf16 or fp32 (row stride ld); score_in [B*K] fp32 is the
+ * raw sum of log-probabilities (-inf: empty slot); flen_in [B*K] int32 is 0 for a live row, else
+ * the number of generated tokens of a finished one (its end token included); len_norm[n] (fp32,
+ * at least step + 2 entries, positive) multiplies the raw score of an n-token hypothesis; step
+ * counts from 0; eos = -1: no end token; t0 = cache position of the first generated token.
+ *   candidates: a live row r offers (r, v) for every v < V with raw = score_in[r] + logp(v)
+ *     (fp32 log-softmax with max subtraction) and length step + 1, finished (flen = step + 1)
+ *     when v == eos; a finished row offers only (r, eos) with its own raw and flen; an empty
+ *     row offers nothing.
+ *   selection: key = raw * len_norm[length] in fp32; the K largest keys of the item win, ties
+ *     to the lower parent slot, then to the lower token id.  Output slot i holds the i-th best:
+ *     tok_out int64, parent_out int32 (slot within the item), score_out = raw, flen_out.  Slots
+ *     past the last candidate are empty: score -inf, tok eos (0 without one), parent = own
+ *     slot, flen 0.
+ *   src_out[r'][t] = src_in[b*K + parent][t] for t < t0 + step and src_out[r'][t0 + step] = r'
+ *     (the new token's K/V go into its own cache row at the next decoder step).  src_in and
+ *     src_out are distinct int32 [B*K, src_ld] tables, src_ld > t0 + step.
+ * workspace: gvl_beam_step_workspace_size(B, K) bytes.  Two launches, no synchronisation. */
+int gvl_attn_decode_beam(const void* q, int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st,
+                         const void* v, int64_t v_sb, int64_t v_st, void* o, int64_t o_sb,
+                         int64_t B, int64_t H, int64_t Tk, float scale, const int32_t* src,
+                         int64_t src_ld, gvl_stream_t stream);
+int64_t gvl_beam_step_workspace_size(int64_t B, int32_t K);
+int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B, int32_t K,
+                  int64_t V, const float* score_in, const int32_t* flen_in, const float* len_norm,
+                  int32_t step, int32_t eos, int64_t t0, const int32_t* src_in, int64_t src_ld,
+                  int64_t* tok_out, int32_t* parent_out, float* score_out, int32_t* flen_out,
+                  int32_t* src_out, void* workspace, gvl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Small fused elementwise helpers on the hot path. */
 /* Column sums of a bf16 [rows][cols] matrix (row stride ld) -> bf16 out[cols]
