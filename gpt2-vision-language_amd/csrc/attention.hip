@@ -146,14 +146,7 @@ GVL_DEV short8_t load_frag_global(const bf16_t* rowptr, int s, int lane, bool ok
 // spread over the lane groups): two VALU lane swaps (v_permlane16_swap / v_permlane32_swap, no
 // LDS crossbar).  __shfl_xor lowered to ds_bpermute_b32 with an lgkmcnt(0) wait each, i.e. two
 // LDS round trips per query group and key tile on the softmax's critical path.
-#ifndef GVL_ATTN_LDS_SHFL  // 1: the round-4 __shfl_xor form (A/B variant builds only)
-#define GVL_ATTN_LDS_SHFL 0
-#endif
 GVL_DEV float rowmax4(float x) {
-  if (GVL_ATTN_LDS_SHFL) {
-    x = fmaxf(x, __shfl_xor(x, 16, 64));
-    return fmaxf(x, __shfl_xor(x, 32, 64));
-  }
   const uint32_t u = __float_as_uint(x);
   const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
   const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
@@ -170,15 +163,7 @@ GVL_DEV short8_t pack_frag(const float4_t& a, const float4_t& b) {
 // ------------------------------------------------------------------------------------
 // Short sequences (G = 1, no dropout) compile for 4 waves per SIMD (<= 128 VGPRs, no spill):
 // 4 blocks per CU instead of 3, so the caption decoder's 1536 (b, h) blocks take 1.5 rounds.
-// Timing-only diagnostic builds of the forward (wrong results; never the shipped library):
-// GVL_ATTN_FWD_DIAG=1 replaces the softmax exponentials by a multiply, 2 drops the in-loop K/V
-// loads and LDS stores, 3 drops the per-tile __syncthreads.
-#ifndef GVL_ATTN_FWD_DIAG
-#define GVL_ATTN_FWD_DIAG 0
-#endif
-#ifndef GVL_ATTN_ONE_BPC  // blocks per CU the one-tile forward is compiled for
-#define GVL_ATTN_ONE_BPC 6
-#endif
+constexpr int ATTN_ONE_BPC = 6;  // blocks per CU the one-tile forward is compiled for
 // ONE (Tk <= 64: one key tile, G = 1): a single LDS stage (16 KiB) and a 6-blocks-per-CU register
 // budget, so the caption decoders' 1536 (b, h) blocks of T = 63 are one round of 256 CUs (4 blocks
 // per CU by registers and 5 by LDS made it 1.5 rounds).
@@ -186,7 +171,7 @@ GVL_DEV short8_t pack_frag(const float4_t& a, const float4_t& b) {
 // bridge's 32 queries): 2 waves over 32-row Q / K / V tiles instead of 4 waves over 64-row ones
 // half of which were padding.
 template <int G, bool DROP, bool ONE = false, int R = 64, int RK = R>  // R: query rows, RK: key rows
-__global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G == 1 && !DROP) ? 4 : 2)) void attn_fwd_kernel(AttnP p) {
+__global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1 && !DROP) ? 4 : 2)) void attn_fwd_kernel(AttnP p) {
   static_assert(!ONE || G == 1, "one-tile forward: G = 1");
   static_assert((R == 64 && RK == 64) || (R == 32 && ONE && (RK == 32 || RK == 64)), "tile rows");
   constexpr int NG = RK / 16, NKS = RK / 32;  // key groups of 16, 32-deep k-steps per key tile
@@ -222,16 +207,9 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
   const int nkt0 = (int)((kend + KT - 1) / KT);
   const int nkt = ONE ? (nkt0 > 0 ? 1 : 0) : nkt0;
 
-#ifndef GVL_ATTN_FWD_V2
-#define GVL_ATTN_FWD_V2 1
-#endif
-#if GVL_ATTN_FWD_V2
   // o[g][4] = row sum of the bf16 P (an MFMA against a ones fragment: the softmax
   // denominator of exactly the P values that enter P.V, and 16 fewer VALU adds per tile)
   constexpr int NO = 5;
-#else
-  constexpr int NO = 4;
-#endif
   float4_t o[G][NO];
   float m[G], l[G];
 #pragma unroll
@@ -253,7 +231,7 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
   __syncthreads();
 
   for (int kt = 0; kt < nkt; ++kt) {
-    const bool more = !ONE && GVL_ATTN_FWD_DIAG != 2 && kt + 1 < nkt;
+    const bool more = !ONE && kt + 1 < nkt;
     if (more) {
       load_rows<R * 4, NC>(rk, kbase, p.k_st, (int64_t)(kt + 1) * KT, p.Tk, tid);
       load_rows<R * 4, NC>(rv, vbase, p.v_st, (int64_t)(kt + 1) * KT, p.Tk, tid);
@@ -300,7 +278,6 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
         mx = fmaxf(fmaxf(mx, sc[g][NG - 1][2]), sc[g][NG - 1][3]);
       }
       mx = rowmax4(mx);
-#if GVL_ATTN_FWD_V2
       // deferred rescale (T13): keep the running max while no row's max grew by more than
       // RESCALE_LOG2 (P then stays <= 2^4 before normalisation); rescale O and the row sum
       // only when some row of the wave needs it — every P of this tile is exponentiated
@@ -318,24 +295,13 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
       }
       const float msub = (m[g] == -INFINITY) ? 0.f : m[g];
       float ls = 0.f;  // (dropout: the denominator counts the un-dropped probabilities)
-#else
-      const float mnew = fmaxf(m[g], mx * p.c2);
-      const float msub = (mnew == -INFINITY) ? 0.f : mnew;
-      const float alpha = __builtin_amdgcn_exp2f(m[g] - msub);
-      m[g] = mnew;
-      float ls = 0.f;
-#endif
       const uint64_t drow = (((uint64_t)b * p.H + h) * p.Tq + (uint64_t)q[g]) * (uint64_t)p.Tk;
 #pragma unroll
       for (int n = 0; n < NG; ++n)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-#if GVL_ATTN_FWD_DIAG == 1
-          const float e = fmaf(sc[g][n][r], p.c2, -msub) * 1e-3f;
-#else
           const float e = __builtin_amdgcn_exp2f(fmaf(sc[g][n][r], p.c2, -msub));
-#endif
-          if (!GVL_ATTN_FWD_V2 || DROP) ls += e;
+          if (DROP) ls += e;
           float pe = e;
           if constexpr (DROP) {
             const int64_t key = k0 + 16 * n + 4 * Gl + r;
@@ -343,16 +309,9 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
           }
           sc[g][n][r] = pe;
         }
-#if !GVL_ATTN_FWD_V2
-      l[g] = l[g] * alpha + ls;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) o[g][t] *= alpha;
-#endif
       pf[g][0] = pack_frag(sc[g][0], sc[g][1]);
       if constexpr (NKS == 2) pf[g][1] = pack_frag(sc[g][NG - 2], sc[g][NG - 1]);
-#if GVL_ATTN_FWD_V2
       if constexpr (DROP) l[g] += ls;
-#endif
     }
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
@@ -362,30 +321,22 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : GVL_ATTN_ONE_BPC) : ((G 
 #pragma unroll
         for (int g = 0; g < G; ++g) o[g][t] = mfma16(vf, pf[g][s], o[g][t]);
       }
-#if GVL_ATTN_FWD_V2
       if constexpr (!DROP) {
 #pragma unroll
         for (int g = 0; g < G; ++g) o[g][4] = mfma16(ones, pf[g][s], o[g][4]);
       }
-#endif
     }
     if (more) {
       store_rows<false, R * 4, NC>(rk, smem[ONE ? 0 : ((kt + 1) & 1)][0], tid);
       store_rows<true, R * 4, NC>(rv, smem[ONE ? 0 : ((kt + 1) & 1)][1], tid);
     }
-#if GVL_ATTN_FWD_DIAG == 3
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     __syncthreads();
-#endif
   }
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     float lt = l[g];
     lt = swap32_reduce<false>(swap16_reduce<false>(lt));  // lanes l, l^16, l^32, l^48 (VALU swaps)
-#if GVL_ATTN_FWD_V2
     if constexpr (!DROP) lt = o[g][4][0];
-#endif
     if (!qok[g]) continue;
     const float inv = 1.f / lt;
     bf16_t* orow = p.o + b * p.o_sb + h * p.o_sh + q[g] * p.o_st;
@@ -1127,17 +1078,9 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_dma_kernel(AttnP p) {
 // [query][key] tiles; phase 2 (wave w = keys 16w..16w+15) reads them transposed
 // (ds_read_b64_tr_b16 gives the same permuted k-slot order as the dK/dV kernel's registers) for
 // dV = P^T dO and dK = dS^T Q.  One launch instead of three, and S / dP computed once.
-// GVL_ATTN_SHORT_LDS32 (default 1): P and dS are written over the V and K tiles once every wave
-// is past its last K / V read (one more barrier), so a block needs 32 KiB of LDS instead of
-// 48: five blocks per CU instead of three (1536 (b, h) blocks: 1.2 rounds instead of 2).
-#ifndef GVL_ATTN_SHORT_LDS32
-#define GVL_ATTN_SHORT_LDS32 1
-#endif
-// GVL_ATTN_SHORT_DIAG=1: timing-only build of the short backward (wrong results; never the shipped
-// library): every load, then dQ / dK / dV stores of the loaded bytes — the kernel's memory floor.
-#ifndef GVL_ATTN_SHORT_DIAG
-#define GVL_ATTN_SHORT_DIAG 0
-#endif
+// P and dS are written over the V and K tiles once every wave is past its last K / V read (one
+// more barrier), so a block needs 32 KiB of LDS instead of the 48 of four separate tiles: five
+// blocks per CU instead of three (1536 (b, h) blocks: 1.2 rounds instead of 2).
 template <int NCK>
 struct ShortIn {  // one (b, h)'s operands of the short backward, loaded ahead of its math
   uint4 rq[2], rk[NCK], rv[NCK], rd[2], oa[2];
@@ -1168,15 +1111,14 @@ GVL_DEV void bwd_short_load(const AttnP& p, const AttnG& gg, int64_t bh, ShortIn
 }
 
 // One (b, h) of the short backward from its loaded operands (bwd_short_load); smem: the Q / dO
-// tiles of R rows, the K / V tiles of RK rows, and P / dS ([query][key], R rows) over V / K (L32)
-// or after them.  R = RK = 64: 4 waves (16 queries / keys each); R = 32 (Tq <= 32): 2 waves over
+// tiles of R rows, the K / V tiles of RK rows, and later P / dS ([query][key], R rows) over V / K.
+// R = RK = 64: 4 waves (16 queries / keys each); R = 32 (Tq <= 32): 2 waves over
 // 32-row query tiles, each wave taking RK / 32 key groups of 16 in phase 2; RK = 32 (Tk <= 32):
 // one 32-deep k-step over the keys where 64 take two.
 template <bool DROP, int R, int RK>
 GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const ShortIn<2 * RK / R>& in,
                             char* smem0, uint64_t seed_) {
   static_assert((R == 64 && RK == 64) || (R == 32 && (RK == 32 || RK == 64)), "short tile rows");
-  constexpr bool L32 = GVL_ATTN_SHORT_LDS32;
   constexpr int TQ = R * D * 2, TK = RK * D * 2;
   constexpr int NG = RK / 16, NKS = RK / 32;  // key groups of 16, 32-deep k-steps over the keys
   constexpr int NQS = R / 32, KPW = RK / R;   // k-steps over the queries; key groups per wave
@@ -1185,8 +1127,8 @@ GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const S
   char* const ks = smem0 + TQ;
   char* const vs = smem0 + TQ + TK;
   char* const ds = smem0 + TQ + 2 * TK;
-  char* const ps = L32 ? vs : smem0 + 2 * TQ + 2 * TK;       // (L32: over V)
-  char* const ss = L32 ? ks : smem0 + 3 * TQ + 2 * TK;       // (L32: over K)
+  char* const ps = vs;  // P over V
+  char* const ss = ks;  // dS over K
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Gl = lane >> 4;
   const int64_t b = bh / p.H, h = bh - b * p.H;
@@ -1196,19 +1138,6 @@ GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const S
   const uint4 (&rq)[2] = in.rq, (&rk)[NCK] = in.rk, (&rv)[NCK] = in.rv, (&rd)[2] = in.rd;
   const uint4 (&oa)[2] = in.oa;
   const float lse_raw = in.lse_raw;
-  if constexpr (GVL_ATTN_SHORT_DIAG == 1 && R == RK) {  // timing-only: the loads, then stores of the same bytes
-    uint32_t x = in.oa[0].x ^ in.oa[1].y ^ __float_as_uint(lse_raw);
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int row = (tid >> 3) + (R / 2) * it, ch = tid & 7;
-      if (row < p.Tq) {
-        *reinterpret_cast<uint4*>(gg.dq + b * gg.dq_sb + h * gg.dq_sh + row * gg.dq_st + ch * 8) = rq[it] ^ make_uint4(x, x, x, x);
-        *reinterpret_cast<uint4*>(gg.dk + b * gg.dk_sb + h * gg.dk_sh + row * gg.dk_st + ch * 8) = rk[it] ^ rd[it];
-        *reinterpret_cast<uint4*>(gg.dv + b * gg.dv_sb + h * gg.dv_sh + row * gg.dv_st + ch * 8) = rv[it];
-      }
-    }
-    return;
-  }
   store_rows<false, R * 4>(rq, qs, tid);
   store_rows<false, R * 4, NCK>(rk, ks, tid);
   store_rows<false, R * 4, NCK>(rv, vs, tid);
@@ -1281,7 +1210,6 @@ GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const S
       *reinterpret_cast<uint2*>(ss + off) = sw[n];
     }
   };
-  if constexpr (!L32) store_p_ds();
   {  // dQ = dS K (lane-local dS fragments, K read transposed)
     const short8_t sf0 = pack_frag(sc[0], sc[1]);
     const short8_t sf1 = NKS == 2 ? pack_frag(sc[NG - 2], sc[NG - 1]) : sf0;
@@ -1300,10 +1228,8 @@ GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const S
                        pack2(acc[t][2] * p.scale, acc[t][3] * p.scale));
     }
   }
-  if constexpr (L32) {  // every wave past its K / V reads, then P / dS over them
-    __syncthreads();
-    store_p_ds();
-  }
+  __syncthreads();  // every wave past its K / V reads, then P / dS over them
+  store_p_ds();
   __syncthreads();
   // phase 2: this lane's key (key groups wave, wave + R / 16 when RK > R); P^T / dS^T fragments
   // in the dK/dV kernel's k-slot order
@@ -1352,8 +1278,7 @@ GVL_DEV void bwd_short_item(const AttnP& p, const AttnG& gg, int64_t bh, const S
 template <bool DROP, int R = 64, int RK = R>
 __global__ __launch_bounds__(R * 4, R == 64 ? 2 : (RK > R ? 3 : 5)) void attn_bwd_short_kernel(AttnP p, AttnG gg) {
   const uint64_t seed_ = DROP ? seed_eff(p.seed, p.seed_ptr) : 0;
-  constexpr bool L32 = GVL_ATTN_SHORT_LDS32;
-  __shared__ __attribute__((aligned(16))) char smem[(L32 ? 2 : 4) * R * D * 2 + 2 * RK * D * 2];
+  __shared__ __attribute__((aligned(16))) char smem[2 * R * D * 2 + 2 * RK * D * 2];
   ShortIn<2 * RK / R> in;
   bwd_short_load<DROP, R, RK>(p, gg, blockIdx.x, in);
   bwd_short_item<DROP, R, RK>(p, gg, blockIdx.x, in, smem, seed_);
@@ -1396,10 +1321,7 @@ int fill(const gvl_attn_desc* d, AttnP& p) {
 // the short caption sequences (31-64 rows) keep 64-row blocks.
 // GVL_ATTN_G=1 keeps 64-row blocks everywhere (A/B of occupancy against rows per block).
 int pick_groups(int64_t T) {
-  static const int forced = [] {
-    const char* e = getenv("GVL_ATTN_G");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = gvl::env_int("GVL_ATTN_G", 0);
   if (forced == 1) return 1;
   return T > 64 ? 2 : 1;
 }
@@ -1407,30 +1329,21 @@ int pick_groups(int64_t T) {
 // Single-launch backward for Tq, Tk <= 64 (attn_bwd_short_kernel); GVL_ATTN_SHORT=0 restores the
 // three-kernel path (A/B measurement).
 bool short_bwd_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("GVL_ATTN_SHORT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_ATTN_SHORT");
   return on;
 }
 
 // LDS-DMA forward (attn_fwd_dma_kernel) for multi-tile key ranges without dropout;
 // GVL_ATTN_FWD_DMA=0: the register-staged attn_fwd_kernel (A/B).
 bool fwd_dma_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("GVL_ATTN_FWD_DMA");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_ATTN_FWD_DMA");
   return on;
 }
 
 // 32-row short backward (attn_bwd_short_kernel<*, 32>) for Tq, Tk <= 32; GVL_ATTN_SHORT32=0: the
 // 64-row kernel (A/B).
 bool short32_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("GVL_ATTN_SHORT32");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_ATTN_SHORT32");
   return on;
 }
 
@@ -1438,21 +1351,23 @@ bool short32_enabled() {
 // 64>) for Tq <= 32 < Tk <= 64 (the cross-attention over 33 image tokens); GVL_ATTN_SHORT3264=0:
 // the 64-row kernels (A/B).
 bool short3264_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("GVL_ATTN_SHORT3264");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_ATTN_SHORT3264");
   return on;
 }
 
 // One-tile forward (attn_fwd_kernel<1, *, true>) for Tk <= 64; GVL_ATTN_FWD_ONE=0: the two-stage
 // kernel (A/B).
 bool fwd_one_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("GVL_ATTN_FWD_ONE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = gvl::env_on("GVL_ATTN_FWD_ONE");
   return on;
+}
+
+// launch(std::bool_constant<DROP>{}) for DROP = has_drop: a route names its kernel once and both
+// dropout instances are built.
+template <typename F>
+void by_drop(const AttnP& p, F launch) {
+  if (p.has_drop) launch(std::true_type{});
+  else launch(std::false_type{});
 }
 
 // Block count of the 1-D heavy-first grid (see tile_of_block); fill() bounds it.
@@ -1470,22 +1385,27 @@ extern "C" int gvl_attn_fwd(const gvl_attn_desc* d, gvl_stream_t stream) {
     if (G == 2) gvl::launch_timed(attn_fwd_dma_kernel<2>, grid, dim3(NT), 0, s, p);
     else gvl::launch_timed(attn_fwd_dma_kernel<1>, grid, dim3(NT), 0, s, p);
   } else if (G == 2) {
-    if (p.has_drop) gvl::launch_timed(attn_fwd_kernel<2, true>, grid, dim3(NT), 0, s, p);
-    else gvl::launch_timed(attn_fwd_kernel<2, false>, grid, dim3(NT), 0, s, p);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_fwd_kernel<2, drop()>, grid, dim3(NT), 0, s, p);
+    });
   } else if (d->Tq <= 32 && d->Tk <= 32 && fwd_one_enabled() && short32_enabled()) {
     dim3 g32(grid_1d(d, 1));
-    if (p.has_drop) gvl::launch_timed(attn_fwd_kernel<1, true, true, 32>, g32, dim3(128), 0, s, p);
-    else gvl::launch_timed(attn_fwd_kernel<1, false, true, 32>, g32, dim3(128), 0, s, p);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_fwd_kernel<1, drop(), true, 32>, g32, dim3(128), 0, s, p);
+    });
   } else if (d->Tq <= 32 && d->Tk <= KT && fwd_one_enabled() && short32_enabled() && short3264_enabled()) {
     dim3 g32(grid_1d(d, 1));
-    if (p.has_drop) gvl::launch_timed(attn_fwd_kernel<1, true, true, 32, 64>, g32, dim3(128), 0, s, p);
-    else gvl::launch_timed(attn_fwd_kernel<1, false, true, 32, 64>, g32, dim3(128), 0, s, p);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_fwd_kernel<1, drop(), true, 32, 64>, g32, dim3(128), 0, s, p);
+    });
   } else if (d->Tk <= KT && fwd_one_enabled()) {
-    if (p.has_drop) gvl::launch_timed(attn_fwd_kernel<1, true, true>, grid, dim3(NT), 0, s, p);
-    else gvl::launch_timed(attn_fwd_kernel<1, false, true>, grid, dim3(NT), 0, s, p);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_fwd_kernel<1, drop(), true>, grid, dim3(NT), 0, s, p);
+    });
   } else {
-    if (p.has_drop) gvl::launch_timed(attn_fwd_kernel<1, true>, grid, dim3(NT), 0, s, p);
-    else gvl::launch_timed(attn_fwd_kernel<1, false>, grid, dim3(NT), 0, s, p);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_fwd_kernel<1, drop()>, grid, dim3(NT), 0, s, p);
+    });
   }
   GVL_LAUNCH_CHECK("gvl_attn_fwd");
   return 0;
@@ -1519,14 +1439,17 @@ extern "C" int gvl_attn_bwd(const gvl_attn_desc* d, const gvl_attn_bwd_desc* gd,
   if (d->Tq <= 64 && d->Tk <= 64 && short_bwd_enabled()) {
     dim3 grid((unsigned)(d->B * d->H));
     if (d->Tq <= 32 && d->Tk <= 32 && short32_enabled()) {
-      if (p.has_drop) gvl::launch_timed(attn_bwd_short_kernel<true, 32>, grid, dim3(128), 0, s, p, g);
-      else gvl::launch_timed(attn_bwd_short_kernel<false, 32>, grid, dim3(128), 0, s, p, g);
+      by_drop(p, [&](auto drop) {
+        gvl::launch_timed(attn_bwd_short_kernel<drop(), 32>, grid, dim3(128), 0, s, p, g);
+      });
     } else if (d->Tq <= 32 && short32_enabled() && short3264_enabled()) {
-      if (p.has_drop) gvl::launch_timed(attn_bwd_short_kernel<true, 32, 64>, grid, dim3(128), 0, s, p, g);
-      else gvl::launch_timed(attn_bwd_short_kernel<false, 32, 64>, grid, dim3(128), 0, s, p, g);
+      by_drop(p, [&](auto drop) {
+        gvl::launch_timed(attn_bwd_short_kernel<drop(), 32, 64>, grid, dim3(128), 0, s, p, g);
+      });
     } else {
-      if (p.has_drop) gvl::launch_timed(attn_bwd_short_kernel<true>, grid, dim3(NT), 0, s, p, g);
-      else gvl::launch_timed(attn_bwd_short_kernel<false>, grid, dim3(NT), 0, s, p, g);
+      by_drop(p, [&](auto drop) {
+        gvl::launch_timed(attn_bwd_short_kernel<drop()>, grid, dim3(NT), 0, s, p, g);
+      });
     }
     GVL_LAUNCH_CHECK("gvl_attn_bwd(short)");
     return 0;
@@ -1535,18 +1458,21 @@ extern "C" int gvl_attn_bwd(const gvl_attn_desc* d, const gvl_attn_bwd_desc* gd,
   const int Gq = pick_groups(d->Tq);
   dim3 gq(grid_1d(d, (d->Tq + 64 * Gq - 1) / (64 * Gq)));
   if (Gq == 2) {
-    if (p.has_drop) gvl::launch_timed(attn_bwd_dq_dma_kernel<2, true>, gq, dim3(NT), 0, s, p, g);
-    else gvl::launch_timed(attn_bwd_dq_dma_kernel<2, false>, gq, dim3(NT), 0, s, p, g);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_bwd_dq_dma_kernel<2, drop()>, gq, dim3(NT), 0, s, p, g);
+    });
   } else {
-    if (p.has_drop) gvl::launch_timed(attn_bwd_dq_dma_kernel<1, true>, gq, dim3(NT), 0, s, p, g);
-    else gvl::launch_timed(attn_bwd_dq_dma_kernel<1, false>, gq, dim3(NT), 0, s, p, g);
+    by_drop(p, [&](auto drop) {
+      gvl::launch_timed(attn_bwd_dq_dma_kernel<1, drop()>, gq, dim3(NT), 0, s, p, g);
+    });
   }
   GVL_LAUNCH_CHECK("gvl_attn_bwd(dq)");
   // dK/dV: 16 keys per wave (32 measured no faster at T = 1024: 2 instead of 3 blocks per CU,
   // profiles/r3/attn_g_ab_r3s2.txt)
   dim3 gk(grid_1d(d, (d->Tk + 63) / 64));
-  if (p.has_drop) gvl::launch_timed(attn_bwd_dkdv_dma_kernel<1, true>, gk, dim3(NT), 0, s, p, g);
-  else gvl::launch_timed(attn_bwd_dkdv_dma_kernel<1, false>, gk, dim3(NT), 0, s, p, g);
+  by_drop(p, [&](auto drop) {
+    gvl::launch_timed(attn_bwd_dkdv_dma_kernel<1, drop()>, gk, dim3(NT), 0, s, p, g);
+  });
   GVL_LAUNCH_CHECK("gvl_attn_bwd(dkdv)");
   return 0;
 }

@@ -11,32 +11,7 @@
 
 namespace {
 
-#ifndef GVL_CE_NT  // threads per row (A/B: 1024 holds 8 chunks per thread instead of 16)
-#define GVL_CE_NT 512
-#endif
-constexpr int CE_NT = GVL_CE_NT;
-// cache policy A/B (build time): GVL_CE_LDNT=1 nontemporal logit loads, GVL_CE_STNT=1
-// nontemporal dlogits stores
-#ifndef GVL_CE_LDNT
-#define GVL_CE_LDNT 0
-#endif
-#ifndef GVL_CE_STNT
-#define GVL_CE_STNT 0
-#endif
-typedef uint32_t ce_u32x4 __attribute__((ext_vector_type(4)));
-GVL_DEV uint4 ce_load(const bf16_t* p) {
-  if constexpr (GVL_CE_LDNT)
-    return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ce_u32x4*>(p)));
-  return *reinterpret_cast<const uint4*>(p);
-}
-GVL_DEV void ce_store(bf16_t* p, uint4 v) {
-  if constexpr (GVL_CE_STNT) __builtin_nontemporal_store(__builtin_bit_cast(ce_u32x4, v), reinterpret_cast<ce_u32x4*>(p));
-  else *reinterpret_cast<uint4*>(p) = v;
-}
-// row max / sum wave steps by DPP + lane swaps (common.h wave_max_v / wave_sum_v); 0: LDS permutes
-#ifndef GVL_CE_DPP
-#define GVL_CE_DPP 1
-#endif
+constexpr int CE_NT = 512;  // threads per row (1024 would hold 8 chunks per thread instead of 16)
 constexpr int CE_MAXC = 8192 / CE_NT;  // 16-B chunks per thread: V <= 65536
 constexpr float CE_L2E = 1.4426950408889634f;
 
@@ -88,14 +63,15 @@ __global__ __launch_bounds__(CE_NT) void ce_row_kernel(
   for (int i = 0; i < CE_MAXC; ++i) {
     const int c = tid + i * CE_NT;
     if (c < nch) {
-      buf[i] = ce_load(src + (int64_t)c * 8);
+      buf[i] = *reinterpret_cast<const uint4*>(src + (int64_t)c * 8);
       if ((int64_t)c * 8 + 8 > V) buf[i] = mask_tail(buf[i], V - (int64_t)c * 8);
       const uint32_t w[4] = {buf[i].x, buf[i].y, buf[i].z, buf[i].w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) mx = fmaxf(mx, fmaxf(lo_bf(w[k]), hi_bf(w[k])));
     }
   }
-  mx = block_max<CE_NT, GVL_CE_DPP>(mx, red);
+  // wave steps of the row max / sum by DPP + lane swaps (common.h wave_max_v / wave_sum_v)
+  mx = block_max<CE_NT, true>(mx, red);
   const float mxl = mx * CE_L2E;
   float s = 0.f;
 #pragma unroll
@@ -109,7 +85,7 @@ __global__ __launch_bounds__(CE_NT) void ce_row_kernel(
              __builtin_amdgcn_exp2f(fmaf(hi_bf(w[k]), CE_L2E, -mxl));
     }
   }
-  s = block_sum<CE_NT, GVL_CE_DPP>(s, red);
+  s = block_sum<CE_NT, true>(s, red);
   const float lse = mx + __logf(s);
   if (tid == 0) row_loss[r] = lse - bf2f(src[tgt]);
   if (dst) {
@@ -129,7 +105,7 @@ __global__ __launch_bounds__(CE_NT) void ce_row_kernel(
           if (base + 2 * k + 1 == tgt) b -= 1.f;
           o[k] = pack2(a, b);
         }
-        ce_store(dst + base, make_uint4(o[0], o[1], o[2], o[3]));
+        *reinterpret_cast<uint4*>(dst + base) = make_uint4(o[0], o[1], o[2], o[3]);
       }
     }
   }

@@ -170,18 +170,14 @@ GemmEnv& env() {
   return e;
 }
 
-// Tile rows per L2 group of the tile walk (gemm_tile_of).  GVL_GEMM_WALK_RULE (A/B, build
-// time): 0 = 8 everywhere; 1 = 4 for M >= 12288 (the LM's 16384-token GEMMs), else 8;
-// 2 (default) = 4 for M or K >= 12288 (also the LM's weight gradients over 16384 tokens), else
-// 8 — LM step 856k -> 862k tokens/s, Q-Former unchanged (profiles/r3/gemm_walk_group_ab_r3s2.txt).
-// GVL_GEMM_GROUP=n overrides it for every GEMM.
-#ifndef GVL_GEMM_WALK_RULE
-#define GVL_GEMM_WALK_RULE 2
-#endif
+// Tile rows per L2 group of the tile walk (gemm_tile_of): 4 for M or K >= 12288 (the LM's
+// 16384-token GEMMs and its weight gradients over 16384 tokens), else 8.  Measured against 8
+// everywhere and against 4 for M >= 12288 only: LM step 856k -> 862k tokens/s, Q-Former
+// unchanged (profiles/r3/gemm_walk_group_ab_r3s2.txt).  GVL_GEMM_GROUP=n overrides it for
+// every GEMM.
 int gemm_group(const gvl_gemm_desc* d) {
   if (env().group > 0) return env().group;
-  if (GVL_GEMM_WALK_RULE == 1 && d->m >= 12288) return 4;
-  if (GVL_GEMM_WALK_RULE == 2 && (d->m >= 12288 || d->k >= 12288)) return 4;
+  if (d->m >= 12288 || d->k >= 12288) return 4;
   return 8;
 }
 

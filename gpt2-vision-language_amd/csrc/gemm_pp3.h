@@ -23,11 +23,6 @@ using namespace gvl_ring;
 // Split-K: work item w = (tile w / splits, K-slice w % splits), every slice kper deep (the
 // host only splits when K divides evenly); slices store fp32 partials, gemm_splitk_reduce
 // applies the epilogue.  KC = 1, bf16 output.
-// Timing-only diagnostic builds (wrong results; never the shipped library): GVL_PP3_DIAG=1
-// stores the plain accumulators (no epilogue operands, math or side output), 2 stores nothing.
-#ifndef GVL_PP3_DIAG
-#define GVL_PP3_DIAG 0
-#endif
 // s_waitcnt vmcnt(n * PER + X) for a runtime n in [0, MAXN]
 template <int PER, int MAXN, int X>
 GVL_DEV void wait_vm_steps_x(int n) {
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp3_kernel(GemmP p) {
   constexpr bool CNT = CntEpi<EPI>::ON;
   constexpr int CNT_S = cnt_stores<FM, FN, EPI>();
   static_assert(!CNT || (NS - 2) * (IPW0 > IPW1 ? IPW0 : IPW1) + CNT_S <= 63, "vmcnt range");
-  const bool cnt_on = CNT && p.cnt && GVL_PP3_DIAG == 0;
+  const bool cnt_on = CNT && p.cnt;
   const uint32_t bias_lds = (uint32_t)(NS * SLOT);
   const __amdgpu_buffer_rsrc_t rc_cnt = uniform_rsrc(p.C, CNT ? p.M * p.ldc * 2 : 0);
   const __amdgpu_buffer_rsrc_t rp_cnt =
@@ -310,15 +305,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp3_kernel(GemmP p) {
     }                                                                                        \
     if (epi_) {                                                                              \
       void* c_ = p.batch > 1 ? p.Cb[cu_bi] : p.C;                                           \
-      if constexpr (GVL_PP3_DIAG == 1) {                                                     \
-        EpiPre<FM, FN, EPI_PLAIN> pp_;                                                       \
-        gemm_epilogue16<FM, FN, EPI_PLAIN>(p, acc, cu_m0 + arow, cu_n0 + bcol, lane, alpha,  \
-                                           pp_, c_, nullptr);                                \
-      } else if constexpr (GVL_PP3_DIAG == 2) {                                              \
-        _Pragma("unroll") for (int i_ = 0; i_ < FM; ++i_)                                    \
-          _Pragma("unroll") for (int j_ = 0; j_ < FN; ++j_)                                  \
-            asm volatile("" ::"v"(acc[i_][j_]));                                             \
-      } else if (CNT && cnt_on) {                                                            \
+      if (CNT && cnt_on) {                                                                   \
         if (p.st_nt)                                                                         \
           gemm_epilogue_cnt<FM, FN, EPI, CNT_NT>(p, acc, cu_m0 + arow, cu_n0 + bcol, lane, alpha, \
                                                  bias_lds, rc_cnt, rp_cnt);                  \
@@ -456,20 +443,12 @@ int launch_pp3_bn(const GemmP& p0, const gvl::GemmSink& k) {
 
 // LDS ring depth per tile shape (slots of 32-deep K-steps; NS - 1 steps in flight):
 // 4 x 32 KiB for 256x256, 4 x 28 KiB for 256x192, 4 x 20 KiB for 128x192.
-#ifndef GVL_PP3_NS_256
-#define GVL_PP3_NS_256 4
-#endif
-#ifndef GVL_PP3_NS_192
-#define GVL_PP3_NS_192 4
-#endif
-#ifndef GVL_PP3_NS_128
-#define GVL_PP3_NS_128 4
-#endif
+constexpr int PP3_NS = 4;
 template <int NS, bool AMN, bool BMN, int EPI>
 int launch_pp3(const GemmP& p, const gvl::GemmSink& s) {
-  if (p.bm == 128) return launch_pp3_bn<GVL_PP3_NS_128, AMN, BMN, EPI, 192, 128>(p, s);
-  return p.bn == 192 ? launch_pp3_bn<GVL_PP3_NS_192, AMN, BMN, EPI, 192, 256>(p, s)
-                     : launch_pp3_bn<GVL_PP3_NS_256, AMN, BMN, EPI, 256, 256>(p, s);
+  if (p.bm == 128) return launch_pp3_bn<NS, AMN, BMN, EPI, 192, 128>(p, s);
+  return p.bn == 192 ? launch_pp3_bn<NS, AMN, BMN, EPI, 192, 256>(p, s)
+                     : launch_pp3_bn<NS, AMN, BMN, EPI, 256, 256>(p, s);
 }
 
 template <int NS, bool AMN, bool BMN>

@@ -2,5 +2,5 @@
 #include "gemm_pp3.h"
 
 namespace gvl {
-int gemm_pp3_launch_ff(const GemmP& p, const GemmSink& k) { return launch_pp3_epi<4, false, false>(p, k); }
+int gemm_pp3_launch_ff(const GemmP& p, const GemmSink& k) { return launch_pp3_epi<PP3_NS, false, false>(p, k); }
 }  // namespace gvl

@@ -134,48 +134,13 @@ struct W4SlabA<96> {
 //   MFMAs of step c; barrier (retires this step's fragment reads and LDS writes).
 // The loop body is unrolled 6 times (register set = step % 3, fragment buffer = step % 2, both
 // static), so K must be a multiple of 6 steps (K % 192 == 0).
-// GVL_W4_IGLP (default 3, measured best of 0-3 on the caption shapes; 0 = off): ask the scheduler to spread the step's LDS reads, LDS writes and global
-// loads between its 24 MFMAs (one wave per SIMD: whatever is not issued in an MFMA's shadow
-// is an MFMA bubble) instead of issuing them as one block ahead of the MFMAs.
-#ifndef GVL_W4_IGLP
-#define GVL_W4_IGLP 3
-#endif
-#if GVL_W4_IGLP == 1  // reads, then writes, then global loads, one per MFMA
-#define W4_INTERLEAVE()                                                           \
-  do {                                                                            \
-    _Pragma("unroll") for (int q_ = 0; q_ < 10; ++q_) {                           \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                          \
-    }                                                                             \
-    _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) {                            \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                          \
-    }                                                                             \
-    _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) {                            \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                          \
-    }                                                                             \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                            \
-  } while (0)
-#elif GVL_W4_IGLP == 2  // global loads first, then reads, then writes
-#define W4_INTERLEAVE()                                                           \
-  do {                                                                            \
-    _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) {                            \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                          \
-    }                                                                             \
-    _Pragma("unroll") for (int q_ = 0; q_ < 10; ++q_) {                           \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                          \
-    }                                                                             \
-    _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) {                            \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                          \
-    }                                                                             \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                            \
-  } while (0)
-#elif GVL_W4_IGLP == 3  // PA+PB rounds of {MFMA, read, MFMA, read, MFMA, load, MFMA, write}
-// (at most FM * FN / 4 rounds: the 128 x 96 tile has 12 MFMAs per step for 4 loads)
+// The scheduler is asked to spread the step's LDS reads, LDS writes and global loads between
+// its 24 MFMAs (one wave per SIMD: whatever is not issued in an MFMA's shadow is an MFMA bubble)
+// instead of issuing them as one block ahead of the MFMAs: PA+PB rounds of {MFMA, read, MFMA,
+// read, MFMA, load, MFMA, write} (at most FM * FN / 4 rounds: the 128 x 96 tile has 12 MFMAs per
+// step for 4 loads).  Measured best on the caption shapes of this pattern, no interleave, "reads,
+// then writes, then loads, one per MFMA" and "loads first, then reads, then writes".  No
+// s_setprio around the MFMAs: it would split the scheduling region.
 #define W4_INTERLEAVE()                                                           \
   do {                                                                            \
     _Pragma("unroll") for (int q_ = 0; q_ < (PA + PB < FM * FN / 4 ? PA + PB : FM * FN / 4); ++q_) { \
@@ -191,29 +156,6 @@ struct W4SlabA<96> {
     if constexpr (FM * FN > 4 * (PA + PB))                                        \
       __builtin_amdgcn_sched_group_barrier(0x008, FM * FN - 4 * (PA + PB), 0);    \
   } while (0)
-#endif
-#if GVL_W4_IGLP
-#define W4_PRIO(x) do {} while (0)  // s_setprio would split the scheduling region
-#else
-#define W4_INTERLEAVE() do {} while (0)
-#define W4_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#endif
-
-// Timing-only diagnostic builds (wrong results; never the shipped library):
-// GVL_W4_DIAG=1 drops the per-step barrier, 2 drops the per-step LDS writes and global loads.
-#ifndef GVL_W4_DIAG
-#define GVL_W4_DIAG 0
-#endif
-#if GVL_W4_DIAG == 1
-#define W4_DIAG_BAR() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-#define W4_DIAG_BAR() barrier_lds()
-#endif
-#if GVL_W4_DIAG == 2
-#define W4_DIAG_MEM(...) do {} while (0)
-#else
-#define W4_DIAG_MEM(...) do { __VA_ARGS__; } while (0)
-#endif
 
 // BM = 192 (6 x 4 fragments per wave) or 128 (4 x 4): the 128-row tile fills the chip when
 // 192-row tiles would leave over a quarter of the CUs idle (3968 / 4096-row caption GEMMs).
@@ -312,115 +254,22 @@ __device__ __forceinline__ void gemm_w4_body(const GemmP& p) {
 #pragma unroll
   for (int i = 0; i < FM; ++i) af[i] = SA::frag(smem, arow + 16 * i, lane);
 
-#ifndef GVL_W4_ORDER
-#define GVL_W4_ORDER 0
-#endif
-#if GVL_W4_ORDER == 3
-// Variant: the step is cut into MFMA chunks pinned in source order by sched_barrier(0), with
-// the step's memory operations placed between them by hand: the LDS writes of step C+2 lead
-// (chunk 0), the global reloads of that register set follow, and the fragment reads of step
-// C+1 are spread over the remaining chunks, so every MFMA gap carries at most a few issues.
-#define W4_SB() __builtin_amdgcn_sched_barrier(0)
 #define GVL_W4_STEP(C, SET, CA, CB, NA, NB)                                                 \
   do {                                                                                      \
-    const char* sl_ = smem + (((SET) + 2) % 3) * SLOT; /* step C+1's slot */                \
-    static_assert(FN == 4, "chunking assumes 4 B fragments");                                \
-    /* chunk 0: writes of step C+2 + MFMA row 0 */                                          \
-    W4_DIAG_MEM(GVL_W4_WRITE((C) + 2, SET));                                                \
-    _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[0][j] = mfma16(CB[j], CA[0], acc[0][j]); \
-    W4_SB();                                                                                \
-    W4_DIAG_MEM(GVL_W4_LOAD(SET));                                                          \
-    _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[1][j] = mfma16(CB[j], CA[1], acc[1][j]); \
-    W4_SB();                                                                                \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                           \
-        NB[j] = SB::frag(sl_ + SA::BYTES, bcol + 16 * j, lane);                             \
-    _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[2][j] = mfma16(CB[j], CA[2], acc[2][j]); \
-    W4_SB();                                                                                \
-    _Pragma("unroll") for (int j = 2; j < 4; ++j)                                           \
-        NB[j] = SB::frag(sl_ + SA::BYTES, bcol + 16 * j, lane);                             \
-    _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[3][j] = mfma16(CB[j], CA[3], acc[3][j]); \
-    W4_SB();                                                                                \
-    _Pragma("unroll") for (int i = 0; i < FM / 2; ++i) NA[i] = SA::frag(sl_, arow + 16 * i, lane); \
-    _Pragma("unroll") for (int i = 4; i < FM; ++i)                                          \
-        _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(CB[j], CA[i], acc[i][j]); \
-    W4_SB();                                                                                \
-    _Pragma("unroll") for (int i = FM / 2; i < FM; ++i) NA[i] = SA::frag(sl_, arow + 16 * i, lane); \
-    W4_DIAG_BAR();                                                                          \
-  } while (0)
-#elif GVL_W4_ORDER == 2
-// Variant: the LDS writes of step C+2 are pinned at the head of the step (sched_barrier), the
-// register set is reloaded after them (no AGPR parking of the staged data), and the step's
-// fragment reads and global loads are spread between its MFMAs.
-constexpr int W4_NR = FM + (BMN ? 2 * FN : FN);  // DS reads per step (tr reads: 2 per B frag)
-#define W4_INTERLEAVE2()                                                          \
-  do {                                                                            \
-    _Pragma("unroll") for (int q_ = 0; q_ < W4_NR; ++q_) {                        \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                          \
-    }                                                                             \
-    _Pragma("unroll") for (int q_ = 0; q_ < PA + PB; ++q_) {                      \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                          \
-    }                                                                             \
-    if constexpr (FM * FN > W4_NR + PA + PB)                                      \
-      __builtin_amdgcn_sched_group_barrier(0x008, FM * FN - W4_NR - PA - PB, 0);  \
-  } while (0)
-#define GVL_W4_STEP(C, SET, CA, CB, NA, NB)                                                 \
-  do {                                                                                      \
-    W4_DIAG_MEM(GVL_W4_WRITE((C) + 2, SET));                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                      \
     { /* step C+1 in slot (SET + 2) % 3 */                                                  \
       const char* sl_ = smem + (((SET) + 2) % 3) * SLOT;                                    \
       _Pragma("unroll") for (int j = 0; j < FN; ++j)                                        \
           NB[j] = SB::frag(sl_ + SA::BYTES, bcol + 16 * j, lane);                           \
       _Pragma("unroll") for (int i = 0; i < FM; ++i) NA[i] = SA::frag(sl_, arow + 16 * i, lane); \
     }                                                                                       \
-    W4_DIAG_MEM(GVL_W4_LOAD(SET));                                                          \
-    _Pragma("unroll") for (int i = 0; i < FM; ++i)                                          \
-        _Pragma("unroll") for (int j = 0; j < FN; ++j)                                      \
-            acc[i][j] = mfma16(CB[j], CA[i], acc[i][j]);                                    \
-    W4_INTERLEAVE2();                                                                       \
-    W4_DIAG_BAR();                                                                          \
-  } while (0)
-#elif GVL_W4_ORDER == 1
-// Variant: the LDS writes of step C+2 lead the step (right after the barrier that retired
-// slot (C+2)%3's reads), so their VGPR->LDS transfer overlaps the MFMAs instead of queueing
-// behind them before the barrier; the register set is reloaded after the fragment reads.
-#define GVL_W4_STEP(C, SET, CA, CB, NA, NB)                                                 \
-  do {                                                                                      \
-    W4_DIAG_MEM(GVL_W4_WRITE((C) + 2, SET));                                                \
-    { /* step C+1 in slot (SET + 2) % 3 */                                                  \
-      const char* sl_ = smem + (((SET) + 2) % 3) * SLOT;                                    \
-      _Pragma("unroll") for (int j = 0; j < FN; ++j)                                        \
-          NB[j] = SB::frag(sl_ + SA::BYTES, bcol + 16 * j, lane);                           \
-      _Pragma("unroll") for (int i = 0; i < FM; ++i) NA[i] = SA::frag(sl_, arow + 16 * i, lane); \
-    }                                                                                       \
-    W4_DIAG_MEM(GVL_W4_LOAD(SET));                                                          \
+    GVL_W4_WRITE((C) + 2, SET);                                                             \
+    GVL_W4_LOAD(SET);                                                                       \
     _Pragma("unroll") for (int i = 0; i < FM; ++i)                                          \
         _Pragma("unroll") for (int j = 0; j < FN; ++j)                                      \
             acc[i][j] = mfma16(CB[j], CA[i], acc[i][j]);                                    \
     W4_INTERLEAVE();                                                                        \
-    W4_DIAG_BAR();                                                                          \
+    barrier_lds();                                                                          \
   } while (0)
-#else
-#define GVL_W4_STEP(C, SET, CA, CB, NA, NB)                                                 \
-  do {                                                                                      \
-    { /* step C+1 in slot (SET + 2) % 3 */                                                  \
-      const char* sl_ = smem + (((SET) + 2) % 3) * SLOT;                                    \
-      _Pragma("unroll") for (int j = 0; j < FN; ++j)                                        \
-          NB[j] = SB::frag(sl_ + SA::BYTES, bcol + 16 * j, lane);                           \
-      _Pragma("unroll") for (int i = 0; i < FM; ++i) NA[i] = SA::frag(sl_, arow + 16 * i, lane); \
-    }                                                                                       \
-    W4_DIAG_MEM(GVL_W4_WRITE((C) + 2, SET); GVL_W4_LOAD(SET));                              \
-    W4_PRIO(1);                                                                             \
-    _Pragma("unroll") for (int i = 0; i < FM; ++i)                                          \
-        _Pragma("unroll") for (int j = 0; j < FN; ++j)                                      \
-            acc[i][j] = mfma16(CB[j], CA[i], acc[i][j]);                                    \
-    W4_PRIO(0);                                                                             \
-    W4_INTERLEAVE();                                                                        \
-    W4_DIAG_BAR();                                                                          \
-  } while (0)
-#endif
 
   int c = 0;
   for (int t = 0; t < ntl; ++t) {
@@ -465,9 +314,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4r_kernel(GemmP p) {
   gemm_w4_body<NS, BMN, EPI, 96, 128>(p);
 }
 
-#ifndef GVL_W4_NS
-#define GVL_W4_NS 3
-#endif
+constexpr int W4_NS = 3;  // LDS ring slots (gemm_w4_body's ring geometry)
 
 // Tile walk: XCD-contiguous work items, then groups of `group` tile rows walked row-fastest.
 // GVL_W4_GROUP=1 walks all column tiles of a row block before the next one, so an XCD reads
@@ -480,10 +327,10 @@ int w4_group(int dflt) {
 // the kernel of a tile shape (if constexpr: only the chosen one is instantiated)
 template <int BM, int BN, bool BMN, int EPI>
 constexpr auto w4_kernel_of() {
-  if constexpr (BN == 96) return gemm_w4n_kernel<GVL_W4_NS, BMN, EPI>;
-  else if constexpr (BM == 96) return gemm_w4r_kernel<GVL_W4_NS, BMN, EPI>;
-  else if constexpr (BM == 192) return gemm_w4_kernel<GVL_W4_NS, BMN, EPI>;
-  else return gemm_w4m_kernel<GVL_W4_NS, BMN, EPI>;
+  if constexpr (BN == 96) return gemm_w4n_kernel<W4_NS, BMN, EPI>;
+  else if constexpr (BM == 96) return gemm_w4r_kernel<W4_NS, BMN, EPI>;
+  else if constexpr (BM == 192) return gemm_w4_kernel<W4_NS, BMN, EPI>;
+  else return gemm_w4m_kernel<W4_NS, BMN, EPI>;
 }
 template <int BM, int BN>
 constexpr const char* w4_kernel_name() {
@@ -492,7 +339,7 @@ constexpr const char* w4_kernel_name() {
 
 template <bool BMN, int EPI, int BM, int BN = W4_BN>
 int launch_w4_bm(const GemmP& p0, const gvl::GemmSink& k) {
-  constexpr int NS = GVL_W4_NS;
+  constexpr int NS = W4_NS;
   if (gvl::gemm_name_only(k, "%s<%d, %s, %d>", w4_kernel_name<BM, BN>(), NS, gvl::tf(BMN), EPI)) return 0;
   GemmP p = p0;
   p.tiles_m = (int)((p.M + BM - 1) / BM);

@@ -96,23 +96,6 @@ struct DImg<true> {
   }
 };
 
-#ifndef GVL_W4D_IGLP
-#define GVL_W4D_IGLP 1
-#endif
-// Timing-only diagnostic builds (wrong results; never the shipped library): GVL_W4D_DIAG=1
-// drops the in-loop A loads, 2 the in-loop B loads and LDS writes, 3 the per-step barrier.
-// GVL_W4D_EPIS_MIN instantiates only the plain and bias+residual epilogues (fast A/B builds).
-#ifndef GVL_W4D_DIAG
-#define GVL_W4D_DIAG 0
-#endif
-// GVL_W4D_AUXPF=1: the epilogue's [M, N] operand (residual / pre_in) is fetched one step ahead
-// of the epilogue (EpiPre FULL) instead of FM / 2 rows at a time inside it — measured slower
-// (Q-Former step 15.09k vs 15.18k images/s, bias+residual GEMM 40.0-40.5 vs 39.4-39.6 us; the
-// held registers make two instances spill), so off (profiles/r3/w4d_auxpf_ab_r3s2.txt)
-#ifndef GVL_W4D_AUXPF
-#define GVL_W4D_AUXPF 0
-#endif
-
 template <bool BMN, int EPI, int BM>
 __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
   constexpr int RW = BM / D_NW, FM = RW / 16, FN = D_BN / 16;
@@ -195,7 +178,7 @@ __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
   tile_coords(0, cu_m0, cu_n0);
   a_offs(cu_m0, oa);
   b_offs(cu_n0, ob);
-  EpiPre<FM, FN, EPI, GVL_W4D_AUXPF> pre;  // bias now; the residual / pre_in tile before the last step
+  EpiPre<FM, FN, EPI> pre;
   pre.load_bias(p, cu_n0, lane);
 
   // prologue: B steps 0..3 (0, 1 written to slots 0, 1; sets 0, 1 reloaded with 2, 3),
@@ -214,7 +197,6 @@ __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
 #pragma unroll
   for (int j = 0; j < FN; ++j) f0[j] = BI::frag(smem, j, 0, lane);
 
-#if GVL_W4D_IGLP
   // One pattern per step: chunk-0 MFMAs interleaved with the staged-B writes, the B reloads
   // and the chunk-1 fragment reads; chunk-1 MFMAs with the next step's chunk-0 reads, then
   // the A reloads (each after the last MFMA reading its registers).
@@ -244,18 +226,13 @@ __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
     }                                                                                        \
     __builtin_amdgcn_sched_group_barrier(0x008, FM * FN, 0);                                 \
   } while (0)
-#else
-#define W4D_SCHED() do {} while (0)
-#endif
 
   // step with A set SA (= step % 3), B staging set SB (= step % 2), LDS slot SL (= step % 3);
   // it reloads B set SB with (OB, KB) and A set SA with (OA, KA)
 #define W4D_STEP(SA, SB, SL, OA, KA, OB, KB)                                                 \
   do {                                                                                       \
-    if constexpr (GVL_W4D_DIAG != 2) {                                                       \
-      W4D_WRITE_B(SB, ((SL) + 2) % 3);                                                       \
-      W4D_LOAD_B(SB, OB, KB);                                                                \
-    }                                                                                        \
+    W4D_WRITE_B(SB, ((SL) + 2) % 3);                                                         \
+    W4D_LOAD_B(SB, OB, KB);                                                                  \
     {                                                                                        \
       const char* sl_ = smem + (SL) * D_SLOT;                                                \
       _Pragma("unroll") for (int j = 0; j < FN; ++j) f1[j] = BI::frag(sl_, j, 1, lane);      \
@@ -270,10 +247,9 @@ __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
     _Pragma("unroll") for (int i = 0; i < FM; ++i)                                           \
       _Pragma("unroll") for (int j = 0; j < FN; ++j)                                         \
         acc[i][j] = mfma16(f1[j], __builtin_bit_cast(short8_t, av[SA][i][1]), acc[i][j]);    \
-    if constexpr (GVL_W4D_DIAG != 1) W4D_LOAD_A(SA, OA, KA);                                 \
+    W4D_LOAD_A(SA, OA, KA);                                                                  \
     W4D_SCHED();                                                                             \
-    if constexpr (GVL_W4D_DIAG == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      \
-    else barrier_lds();                                                                      \
+    barrier_lds();                                                                           \
   } while (0)
 
   for (int t = 0; t < ntl; ++t) {
@@ -299,12 +275,12 @@ __device__ __forceinline__ void gemm_w4d_body(const GemmP& p) {
       W4D_STEP(2, 0, 2, oa, k + 5, nb, 0);
       W4D_STEP(0, 1, 0, na, 0, nb, 1);
       W4D_STEP(1, 0, 1, na, 1, nb, 2);
-      // the epilogue's [M, N] operand (residual / pre_in) for this wave's outputs, one step
-      // ahead of its use instead of FM / XH exposed fetches inside the epilogue (earlier and
-      // the registers it holds make the last block spill)
-      if constexpr (EpiKind<EPI>::AUX && GVL_W4D_AUXPF) pre.load_aux(p, cu_m0 + wave * RW, cu_n0, lane, 0);
       W4D_STEP(2, 1, 2, na, 2, nb, 3);
-      gemm_epilogue16<FM, FN, EPI, GVL_W4D_AUXPF>(p, acc, cu_m0 + wave * RW, cu_n0, lane, alpha, pre);
+      // the epilogue fetches its [M, N] operand (residual / pre_in) FM / 2 rows at a time inside
+      // it: fetching it one step ahead (EpiPre FULL) measured slower (Q-Former step 15.09k vs
+      // 15.18k images/s, bias+residual GEMM 40.0-40.5 vs 39.4-39.6 us; the held registers make
+      // two instances spill; profiles/r3/w4d_auxpf_ab_r3s2.txt)
+      gemm_epilogue16<FM, FN, EPI>(p, acc, cu_m0 + wave * RW, cu_n0, lane, alpha, pre);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -358,11 +334,7 @@ int launch_rows(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
 
 // the epilogues the caption decoders and the Q-Former route to the four-wave kernels
 inline bool epi_supported(int e) {
-#ifdef GVL_W4D_EPIS_MIN
-  return e == EPI_PLAIN || e == EPI_BIAS_RES;
-#else
   return e == EPI_PLAIN || e == EPI_BIAS || e == EPI_BIAS_RES || e == EPI_RES || e == EPI_BIAS_DROP_RES;
-#endif
 }
 
 template <bool BMN>
@@ -370,11 +342,9 @@ int launch_epi(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
   switch (gvl::gemm_epi_kind(p)) {
     case EPI_PLAIN: return launch_rows<BMN, EPI_PLAIN>(p, rows128, s);
     case EPI_BIAS_RES: return launch_rows<BMN, EPI_BIAS_RES>(p, rows128, s);
-#ifndef GVL_W4D_EPIS_MIN
     case EPI_BIAS: return launch_rows<BMN, EPI_BIAS>(p, rows128, s);
     case EPI_RES: return launch_rows<BMN, EPI_RES>(p, rows128, s);
     case EPI_BIAS_DROP_RES: return launch_rows<BMN, EPI_BIAS_DROP_RES>(p, rows128, s);
-#endif
     default: return -1;
   }
 }

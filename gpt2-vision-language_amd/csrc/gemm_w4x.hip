@@ -159,7 +159,7 @@ struct XSlabB<256, MN> {
 // waves of 128 x 128 (8 x 8 fragments = all 256 AGPRs, 0.25 reads per MFMA).
 // GR: a grouped launch (gvl_gemm_grouped): the problems differ in M, N, K and strides
 // (GemmP::Mb.. / gtile), read per tile.
-// Residual folded into the accumulators (GVL_W4X_FOLD, default 1; build-time A/B): for the
+// Residual folded into the accumulators: for the
 // bias + residual epilogue (the LM's attn.c_proj / mlp.c_proj forward, x + yW^T + b with one
 // 256 x 192 tile per CU) the residual tile is read at the tile's start, before the prologue's
 // DMA and while no fragment registers are live (the K-loop has no registers to spare), and
@@ -170,9 +170,6 @@ struct XSlabB<256, MN> {
 // 83.1 us; profiles/r5/w4x_fold_r5q_r5r.txt) — the residual's 25 MB read, wherever it sits in
 // a one-tile-per-CU launch, is most of the rest.  Needs alpha == 1 (the planner sends no other
 // bias + residual GEMM here).
-#ifndef GVL_W4X_FOLD
-#define GVL_W4X_FOLD 1
-#endif
 
 template <int BM, int BN, bool AMN, bool BMN, int EPI, bool GR>
 GVL_DEV void gemm_w4x_body(const GemmP& p) {
@@ -258,7 +255,7 @@ GVL_DEV void gemm_w4x_body(const GemmP& p) {
     pre.load_bias(p, n0 + bcol, lane);
     const int aux_at = nks >= 2 ? nks - 2 : 0;
     // (the planner sends only alpha == 1, >= 12 K-step bias + residual GEMMs here: gemm_w4x_plan)
-    constexpr bool FOLD = GVL_W4X_FOLD && EPI == EPI_BIAS_RES && !GR && !AMN;
+    constexpr bool FOLD = EPI == EPI_BIAS_RES && !GR && !AMN;
     // the residual tile, read before the prologue's DMA (no fragment registers live yet)
     uint2 rx[FOLD ? FM : 1][FOLD ? FN : 1];
     if constexpr (FOLD) {
@@ -488,8 +485,8 @@ bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force) {
   if ( p.c_f32 || p.K % KS != 0 || p.K < 2 * KS || p.N % 8 != 0 || p.ldc % 8 != 0 ||
       p.lda % 8 != 0 || p.ldb % 8 != 0 || (epi != EPI_PLAIN && epi != EPI_BIAS_RES))
     return false;
-  // the folded residual (GVL_W4X_FOLD) needs alpha == 1
-  if (GVL_W4X_FOLD && epi == EPI_BIAS_RES && (p.alpha != 1.f || p.alpha_ptr)) return false;
+  // the folded residual needs alpha == 1
+  if (epi == EPI_BIAS_RES && (p.alpha != 1.f || p.alpha_ptr)) return false;
   (void)b_mn;
   // 256-row tiles where they (nearly) fill the chip, else 128-row tiles
   const int64_t cus = num_cus(), tn = (p.N + 192 - 1) / 192;

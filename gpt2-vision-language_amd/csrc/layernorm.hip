@@ -17,108 +17,18 @@ constexpr int LN_BWD_NT = 256;   // 4 waves, one row each (+1 prefetched)
 // 1024 / 2048 (16384 x 768 22.2-22.5 vs 23.1-23.4 us at 1024, 8064 x 768 15.0 vs 16.5, 4224 x 1024
 // 14.3 vs 15.3, incl. the finalize, back to back; no measurable change inside the steps;
 // profiles/r4/ln_bwd_blocks_r4lnb.txt)
-#ifndef GVL_LN_BWD_MAXB
-#define GVL_LN_BWD_MAXB 512
-#endif
-constexpr int LN_BWD_MAXB = GVL_LN_BWD_MAXB;
+constexpr int LN_BWD_MAXB = 512;
 
-// Row sums by DPP + lane swaps (common.h wave_sum_v / half_sum_v: no ds_bpermute round trips,
-// six per row sum in the __shfl_xor butterflies).
-#ifndef GVL_LN_DPP  // 0: the __shfl_xor butterflies (A/B builds)
-#define GVL_LN_DPP 1
-#endif
-GVL_DEV float half_sum(float v) {  // over the 32 lanes of this half-wave
-  if (GVL_LN_DPP) return half_sum_v(v);
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-GVL_DEV float row_sum64(float v) {  // over the wave
-  if (GVL_LN_DPP) return wave_sum_v(v);
-  return warp_sum(v);
-}
+// Row sums are by DPP + lane swaps (common.h half_sum_v over the 32 lanes of a half-wave,
+// wave_sum_v over the wave): no ds_bpermute round trips, six per row sum in __shfl_xor butterflies.
 
-template <int IT>
-__global__ __launch_bounds__(LN_FWD_NT) void ln_fwd_kernel(const bf16_t* __restrict__ x, int64_t ldx,
-                                                           const bf16_t* __restrict__ w,
-                                                           const bf16_t* __restrict__ b,
-                                                           bf16_t* __restrict__ y, int64_t ldy,
-                                                           float* __restrict__ mean_out,
-                                                           float* __restrict__ rstd_out,
-                                                           int64_t rows, int C, float eps) {
-  const int hl = threadIdx.x & 31;
-  const int64_t row = (int64_t)blockIdx.x * (LN_FWD_NT / 32) + (threadIdx.x >> 5);
-  const bool live = row < rows;  // (no early exit: the half-wave shuffles need both halves)
-  const bf16_t* xr = x + (live ? row : 0) * ldx;
-  float v[IT][8];
-  float s = 0.f;
-  uint4 wq[IT], bq[IT];  // gamma / beta issued with the row loads (their latency overlaps)
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = (hl + 32 * it) * 8;
-    if (c < C) {
-      wq[it] = *reinterpret_cast<const uint4*>(w + c);
-      bq[it] = *reinterpret_cast<const uint4*>(b + c);
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = (hl + 32 * it) * 8;
-    if (live && c < C) {
-      unpack8(*reinterpret_cast<const uint4*>(xr + c), v[it]);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) s += v[it][r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) v[it][r] = 0.f;
-    }
-  }
-  const float mean = half_sum(s) / (float)C;
-  float ss = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = (hl + 32 * it) * 8;
-    if (c < C) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const float d = v[it][r] - mean;
-        ss += d * d;
-      }
-    }
-  }
-  const float rstd = rsqrtf(half_sum(ss) / (float)C + eps);
-  if (!live) return;
-  bf16_t* yr = y + row * ldy;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = (hl + 32 * it) * 8;
-    if (c < C) {
-      float wf[8], bf[8], o[8];
-      unpack8(wq[it], wf);
-      unpack8(bq[it], bf);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) o[r] = (v[it][r] - mean) * rstd * wf[r] + bf[r];
-      *reinterpret_cast<uint4*>(yr + c) = pack8(o);
-    }
-  }
-  if (hl == 0) {
-    if (mean_out) mean_out[row] = mean;
-    if (rstd_out) rstd_out[row] = rstd;
-  }
-}
-
-// Persistent form (default; GVL_LN_FWD_PERSIST=0 builds the one-shot grid above for A/B): at most
-// GVL_LN_FWD_MAXB blocks, each half-wave walks rows r, r + stride, ... and issues the next row's
-// loads before it normalises and stores the current one, so every half-wave keeps a read and a
-// write in flight instead of the whole grid reading first and writing afterwards.  4-7 % faster
-// at 4096-16384 rows (1024 blocks = 2048 the same; 512 slower at 16384 rows), same arithmetic
+// Persistent forward: at most LN_FWD_MAXB blocks, each half-wave walks rows r, r + stride, ... and
+// issues the next row's loads before it normalises and stores the current one, so every half-wave
+// keeps a read and a write in flight instead of the whole grid reading first and writing
+// afterwards.  4-7 % faster at 4096-16384 rows than a one-shot grid of one row per half-wave
+// (1024 blocks = 2048 the same; 512 slower at 16384 rows), same arithmetic
 // (profiles/r5/ln_fwd_persist_r5ln.txt).
-#ifndef GVL_LN_FWD_PERSIST
-#define GVL_LN_FWD_PERSIST 1
-#endif
-#ifndef GVL_LN_FWD_MAXB
-#define GVL_LN_FWD_MAXB 1024
-#endif
+constexpr int LN_FWD_MAXB = 1024;
 template <int IT>
 __global__ __launch_bounds__(LN_FWD_NT) void ln_fwd_persist_kernel(
     const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ w,
@@ -164,7 +74,7 @@ __global__ __launch_bounds__(LN_FWD_NT) void ln_fwd_persist_kernel(
       }
     }
     if (i + 1 < iters) fetch(row + stride);
-    const float mean = half_sum(s) / (float)C;
+    const float mean = half_sum_v(s) / (float)C;
     float ss = 0.f;
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -177,7 +87,7 @@ __global__ __launch_bounds__(LN_FWD_NT) void ln_fwd_persist_kernel(
         }
       }
     }
-    const float rstd = rsqrtf(half_sum(ss) / (float)C + eps);
+    const float rstd = rsqrtf(half_sum_v(ss) / (float)C + eps);
     if (row < rows) {
       bf16_t* yr = y + row * ldy;
 #pragma unroll
@@ -274,7 +184,7 @@ __global__ __launch_bounds__(LN_BWD_NT) void ln_bwd_kernel(
         for (int r = 0; r < 4; ++r) xh[it][r] = g[it][r] = 0.f;
       }
     }
-    const float m1 = row_sum64(s1) / (float)C, m2 = row_sum64(s2) / (float)C;
+    const float m1 = wave_sum_v(s1) / (float)C, m2 = wave_sum_v(s2) / (float)C;
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
       const int c = (lane + 64 * it) * 4;
@@ -396,23 +306,13 @@ extern "C" int gvl_layernorm_fwd(const void* x, int64_t ldx, const void* w, cons
   const auto wp = static_cast<const bf16_t*>(w);
   const auto bp = static_cast<const bf16_t*>(b);
   auto yp = static_cast<bf16_t*>(y);
-  if (GVL_LN_FWD_PERSIST) {
-    const int pg = grid < GVL_LN_FWD_MAXB ? grid : GVL_LN_FWD_MAXB;
-    if (cols <= 768)
-      hipLaunchKernelGGL(ln_fwd_persist_kernel<3>, dim3(pg), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp,
-                         yp, ldy, mean, rstd, rows, (int)cols, eps);
-    else
-      hipLaunchKernelGGL(ln_fwd_persist_kernel<4>, dim3(pg), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp,
-                         yp, ldy, mean, rstd, rows, (int)cols, eps);
-    GVL_LAUNCH_CHECK("gvl_layernorm_fwd");
-    return 0;
-  }
+  const int pg = grid < LN_FWD_MAXB ? grid : LN_FWD_MAXB;
   if (cols <= 768)
-    hipLaunchKernelGGL(ln_fwd_kernel<3>, dim3(grid), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp, yp,
-                       ldy, mean, rstd, rows, (int)cols, eps);
+    hipLaunchKernelGGL(ln_fwd_persist_kernel<3>, dim3(pg), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp,
+                       yp, ldy, mean, rstd, rows, (int)cols, eps);
   else
-    hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3(grid), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp, yp,
-                       ldy, mean, rstd, rows, (int)cols, eps);
+    hipLaunchKernelGGL(ln_fwd_persist_kernel<4>, dim3(pg), dim3(LN_FWD_NT), 0, s, xp, ldx, wp, bp,
+                       yp, ldy, mean, rstd, rows, (int)cols, eps);
   GVL_LAUNCH_CHECK("gvl_layernorm_fwd");
   return 0;
 }

@@ -1148,7 +1148,9 @@ def test_attention_noncausal(cuda, Tq, Tk):
     _attn_case(cuda, 2, 2, Tq, Tk, False, packed=False)
 
 
-@pytest.mark.parametrize("Tq,Tk", [(32, 33), (40, 130), (32, 32), (17, 29), (31, 50)])
+# with dropout: (80, 80) takes the two-group forward and dQ kernels, (48, 60) the 64-row one-tile
+# forward and short backward; the others the 32-row and the one-group multi-tile routes
+@pytest.mark.parametrize("Tq,Tk", [(32, 33), (40, 130), (32, 32), (17, 29), (31, 50), (80, 80), (48, 60)])
 def test_attention_dropout_exact_mask(cuda, Tq, Tk):
     _attn_case(cuda, 2, 2, Tq, Tk, False, packed=False, drop_p=0.1, seed=4242)
 
