@@ -17,7 +17,10 @@ token costs one row through each block:
   * beam search (BeamDecoder, beam_search): B items x K beams share one R = B*K-row cache
     through an int32 indirection table src[r, t] (the row holding position t of hypothesis r),
     so reordering beams rewrites the table (gvl_beam_step) and attention reads through it
-    (gvl_attn_decode_beam); the prefix is prefilled once per item and no cache row is copied.
+    (gvl_attn_decode_beam); the prefix is prefilled once per item and no cache row is copied;
+  * repetition penalty, no-repeat n-gram, minimum length and bad-token bans edit each step's
+    logits in place before the token choice (gvl_logits_process: one launch, a hypothesis'
+    history read through the same src table, only the few logits concerned are touched).
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
@@ -254,47 +257,117 @@ class BeamDecoder(KVDecoder):
             self.src = None
 
 
-def sample_next(logits, *, greedy=False, temperature=1.0, top_k=0, top_p=1.0, generator=None):
-    """Next token ids [B] from logits [B, V] on the gvl_sample kernel."""
+def sample_next(logits, *, greedy=False, temperature=1.0, top_k=0, top_p=1.0, generator=None,
+                out=None):
+    """Next token ids [B] from logits [B, V] on the gvl_sample kernel (into `out` if given)."""
     rows = logits.shape[0]
     if greedy:
         u = torch.zeros(rows, dtype=torch.float32, device=logits.device)
-        return K.sample(logits, u, 1.0, 1, 1.0)
+        return K.sample(logits, u, 1.0, 1, 1.0, out=out)
     u = torch.rand(rows, generator=generator, device=logits.device, dtype=torch.float32)
-    return K.sample(logits, u, temperature, top_k, top_p)
+    return K.sample(logits, u, temperature, top_k, top_p, out=out)
+
+
+class _Controls:
+    """The logits processors of generate / beam_search (gvl_logits_process): what is on, the
+    prompt as part of the penalised sequence, the bad-token list uploaded once."""
+
+    def __init__(self, prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                 bad_tokens, penalize_prompt):
+        self.pen = float(repetition_penalty)
+        self.ngram = int(no_repeat_ngram_size)
+        self.eos = eos
+        self.min_new = int(min_new_tokens) if eos is not None else 0
+        self.bad = None
+        if bad_tokens is not None and len(bad_tokens) > 0:
+            self.bad = torch.as_tensor(bad_tokens).to(device=prompt_ids.device,
+                                                      dtype=torch.int32).contiguous()
+        self.always = self.pen != 1.0 or self.ngram != 0 or self.bad is not None
+        self.prompt = None
+        if penalize_prompt and (self.pen != 1.0 or self.ngram != 0):
+            self.prompt = prompt_ids.to(torch.int64).contiguous()
+
+    def apply(self, logits, hist, step, **kw):
+        ban_eos = step < self.min_new
+        if self.always or ban_eos:
+            K.logits_process(logits, hist, step, prompt=self.prompt,
+                             repetition_penalty=self.pen, no_repeat_ngram_size=self.ngram,
+                             eos=self.eos, ban_eos=ban_eos, bad_tokens=self.bad, **kw)
 
 
 @torch.no_grad()
 def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0, top_k=0,
-             top_p=1.0, generator=None, return_logits=False):
+             top_p=1.0, generator=None, return_logits=False, eos=None, return_lengths=False,
+             repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
+             penalize_prompt=True):
     """KV-cached decode of n_new tokens after prompt_ids [B, P].  greedy: argmax (first max);
     else temperature / top-k / top-p sampling with `generator` (a CUDA torch.Generator).
-    Returns the new ids [B, n_new] (and the per-step logits [B, n_new, V] if asked)."""
+
+    Before the token choice (and before temperature / top-k / top-p, Hugging Face's order) each
+    step's logits pass gvl_logits_process: repetition_penalty (Hugging Face's rule, once per
+    distinct token), no_repeat_ngram_size, bad_tokens (a list or int tensor of banned ids) and,
+    for the first min_new_tokens steps, a ban of `eos`.  penalize_prompt: the prompt ids count as
+    part of the sequence the penalty and the n-gram rule look at.  With the defaults no such
+    kernel runs.  eos: a row that draws it is done, its later tokens are eos, and the loop ends
+    once every row is done (one host read per step, only when eos is given).
+
+    Returns the new ids [B, n_new], then if asked the per-step logits [B, steps that ran, V] as
+    the decoder gave them (before the processors), then if asked lengths [B] int32: the count of
+    tokens up to and including eos, n_new for a row that never ended."""
     B = prompt_ids.shape[0]
     dec = KVDecoder(model, B, n_new)
     logits = dec.start(prompt_ids, z)
-    out, lg = [], []
+    dev = logits.device
+    ctl = _Controls(prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                    bad_tokens, penalize_prompt)
+    hist = torch.empty(n_new, B, dtype=torch.int64, device=dev)
+    lengths = torch.full((B,), n_new, dtype=torch.int32, device=dev)
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    lg, steps = [], n_new
     for i in range(n_new):
         if return_logits:
-            lg.append(logits.float())
+            lg.append(logits.to(torch.float32, copy=True))
+        ctl.apply(logits, hist, i)
         nxt = sample_next(logits, greedy=greedy, temperature=temperature, top_k=top_k,
-                          top_p=top_p, generator=generator)
-        out.append(nxt)
+                          top_p=top_p, generator=generator, out=hist[i])
+        if eos is not None:
+            nxt.copy_(torch.where(done, eos, nxt))
+            ended = (nxt == eos) & ~done
+            lengths = torch.where(ended, i + 1, lengths).to(torch.int32)
+            done |= ended
+            if bool(done.all()):
+                steps = i + 1
+                break
         if i + 1 < n_new:
             logits = dec.step(nxt)
-    ids = torch.stack(out, dim=1)
-    return (ids, torch.stack(lg, dim=1)) if return_logits else ids
+    if steps < n_new:
+        hist[steps:] = eos
+    out = [hist.t().contiguous()]
+    if return_logits:
+        out.append(torch.stack(lg, dim=1))
+    if return_lengths:
+        out.append(lengths)
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 @torch.no_grad()
 def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
-                return_all=False):
+                return_all=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                min_new_tokens=0, bad_tokens=None, penalize_prompt=True):
     """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
     hypotheses per item.  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
     tokens; hypotheses are ranked by raw * n ** -length_penalty (n = its length, end token
     included), ties to the lower parent slot and then the lower token id (gvl_beam_step).  One
     that emits `eos` is finished and competes with its final score; the search ends after n_new
     steps or once every hypothesis is finished (eos=None: never).
+
+    repetition_penalty, no_repeat_ngram_size, min_new_tokens (eos banned for that many steps),
+    bad_tokens and penalize_prompt act as in generate(), per hypothesis: gvl_logits_process reads
+    each live hypothesis' own history through the beam table before every step, and leaves
+    finished ones alone.  The log-probabilities summed into a score are then those of the
+    *processed* distribution (the softmax of the edited logits), as in Hugging Face.  With the
+    defaults no such kernel runs.
+
     Returns (ids [B, n_new] of the best hypothesis, padded with eos past its end, lengths [B],
     raw scores [B]); return_all: all of them in rank order, [B, K, n_new], [B, K], [B, K]."""
     B, Kb = prompt_ids.shape[0], num_beams
@@ -302,6 +375,8 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     dec = BeamDecoder(model, B, Kb, n_new)
     first = dec.start(prompt_ids, z)
     dev, V, t0 = first.device, first.shape[1], dec.t
+    ctl = _Controls(prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                    bad_tokens, penalize_prompt)
     logits = torch.empty(R, V, dtype=first.dtype, device=dev)
     logits.view(B, Kb, V)[:, 0] = first  # slots 1.. start empty (score -inf): never read
     len_norm = torch.arange(n_new + 2, dtype=torch.float32).clamp_(min=1.0).pow_(
@@ -314,21 +389,22 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     parent = torch.empty(R, dtype=torch.int32, device=dev)
     nws = K._L().gvl_beam_step_workspace_size(B, Kb)
     ws = torch.empty(max(nws, 8) // 4, dtype=torch.float32, device=dev)
-    toks, cur = [], 0
+    hist = torch.empty(n_new, R, dtype=torch.int64, device=dev)  # step-major: hist[s] = tok_out
+    S, cur = 0, 0
     for s in range(n_new):
-        tok = torch.empty(R, dtype=torch.int64, device=dev)
+        tok = hist[s]
+        ctl.apply(logits, hist, s, src=src[cur], t0=t0, rows_per_item=Kb, flen=flen[cur])
         K.beam_step(logits, score[cur], flen[cur], len_norm, src[cur], Kb, s, eos, t0,
                     out=(tok, parent, score[1 - cur], flen[1 - cur], src[1 - cur]), workspace=ws)
         cur = 1 - cur
-        toks.append(tok)
+        S = s + 1
         if s + 1 == n_new:
             break
         # finished hypotheses only carry over, in their order: stopping here or later is the same
         if eos is not None and bool(((flen[cur] > 0) | (score[cur] == float("-inf"))).all()):
             break
         logits = dec.step(tok, src[cur])
-    S = len(toks)
-    ids = torch.stack(toks, dim=1).gather(0, src[cur][:, t0:t0 + S].long())
+    ids = hist[:S].t().gather(0, src[cur][:, t0:t0 + S].long())
     if S < n_new:
         ids = torch.cat([ids, ids.new_full((R, n_new - S), eos)], dim=1)
     live = torch.where(score[cur] == float("-inf"), 0, S).to(torch.int32)

@@ -529,6 +529,58 @@ def beam_step(logits2, score, flen, len_norm, src, K, step, eos, t0, out=None, w
     return out
 
 
+def logits_process(logits2, hist, n_hist, *, src=None, t0=0, prompt=None, rows_per_item=1,
+                   repetition_penalty=1.0, no_repeat_ngram_size=0, eos=None, ban_eos=False,
+                   bad_tokens=None, flen=None):
+    """Repetition penalty, no-repeat n-gram, end-token and bad-token bans on logits2 [R, V] bf16 /
+    fp32, in place (include/gvl.h gvl_logits_process).  hist int64 [>= n_hist, >= R]: the
+    generated tokens, one step per row (None with n_hist = 0); src int32 [R, >= t0 + n_hist]: the
+    beam table a row's history is read through (None: its own column); prompt int64
+    [R / rows_per_item, P]; bad_tokens int32 [n]; flen int32 [R]: rows with flen > 0 are left
+    alone.  -> logits2."""
+    _dev(logits2, hist, src, prompt, bad_tokens, flen)
+    _rowmajor(logits2, "logits")
+    R, V = logits2.shape
+    n_hist = int(n_hist)
+    if logits2.dtype not in (BF16, F32):
+        raise ValueError("gvl: logits_process takes bf16 or fp32 logits")
+    hist_ld = 0
+    if n_hist > 0:
+        if hist is None:
+            raise ValueError(f"gvl: logits_process needs hist for n_hist = {n_hist}")
+        _rowmajor(hist, "hist")
+        if hist.dtype != torch.int64 or hist.shape[0] < n_hist or hist.shape[1] < R:
+            raise ValueError("gvl: hist must be an int64 [>= n_hist, >= rows of logits] tensor")
+        hist_ld = hist.stride(0)
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R or src.shape[1] < t0 + n_hist:
+            raise ValueError("gvl: src must be an int32 [rows of logits, >= t0 + n_hist] table")
+    P = 0
+    if prompt is not None:
+        _rowmajor(prompt, "prompt")
+        if (prompt.dtype != torch.int64 or rows_per_item < 1 or
+                prompt.shape[0] * rows_per_item != R):
+            raise ValueError("gvl: prompt must be an int64 [rows of logits / rows_per_item, P] "
+                             "tensor")
+        P = prompt.shape[1]
+    if bad_tokens is not None and (bad_tokens.dtype != torch.int32 or bad_tokens.dim() != 1 or
+                                   not bad_tokens.is_contiguous()):
+        raise ValueError("gvl: bad_tokens must be a contiguous int32 vector")
+    if flen is not None and (flen.dtype != torch.int32 or flen.numel() != R or
+                             not flen.is_contiguous()):
+        raise ValueError("gvl: flen must be a contiguous int32 [rows of logits] vector")
+    n_bad = 0 if bad_tokens is None else bad_tokens.numel()
+    _lib.check(_L().gvl_logits_process(
+        logits2.data_ptr(), logits2.stride(0), int(logits2.dtype == F32), R, V,
+        _p(hist) if n_hist > 0 else None, hist_ld, n_hist, _p(src),
+        0 if src is None else src.stride(0), int(t0), _p(prompt) if P > 0 else None,
+        0 if P == 0 else prompt.stride(0), P, int(rows_per_item), float(repetition_penalty),
+        int(no_repeat_ngram_size), -1 if eos is None else int(eos), int(bool(ban_eos)),
+        _p(bad_tokens) if n_bad > 0 else None, n_bad, _p(flen), _stream()), "gvl_logits_process")
+    return logits2
+
+
 def sample(logits2, u, temperature=1.0, top_k=0, top_p=1.0, out=None):
     """Fused temperature / top-k / top-p draw per row (include/gvl.h gvl_sample); u [rows]
     fp32 uniforms in [0, 1) on the device.  -> int64 [rows]."""

@@ -384,6 +384,41 @@ int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B
                   int64_t* tok_out, int32_t* parent_out, float* score_out, int32_t* flen_out,
                   int32_t* src_out, void* workspace, gvl_stream_t stream);
 
+/* Logits processors: repetition penalty, no-repeat n-gram, end-token and bad-token bans, applied
+ * in place between a decoder step and gvl_sample / gvl_beam_step.  Added at ABI v14 without a
+ * version bump, like the beam entry points: a new symbol, nothing existing changes.
+ *
+ * logits [R, V] bf16 or fp32 (row stride ld >= V, 1 <= V <= 65536).  Row r's token sequence s is
+ * its item's prompt, prompt[(r / rows_per_item)*prompt_ld + 0..P) (int64, prompt_ld >= P; null
+ * with P = 0), then its n_hist generated tokens g_i = hist[i*hist_ld + row_i] (int64, step-major: one step's
+ * tok_out of gvl_beam_step or out of gvl_sample is one row of it; hist_ld >= R), where row_i = r
+ * when src is null, else src[r*src_ld + t0 + i] (the beam table, int32, src_ld >= t0 + n_hist;
+ * the kernel clamps an entry into [0, R), so a bad table cannot read outside hist).
+ * L = P + n_hist <= 4096; rows_per_item >= 1 divides R.  Ids are compared as int32 (one past
+ * int32 saturates); an id outside [0, V) takes part in n-gram matching as a value and never
+ * indexes logits.
+ *   skipped: a row with flen != null and flen[r] > 0 (a finished beam) keeps every bit.
+ *   repetition penalty (rep_penalty = p != 1; p finite, > 0): for each distinct v of s inside
+ *     [0, V), once however often it occurs, x = logits[r][v] as fp32 becomes x < 0 ? x * p : x / p
+ *     (a correctly rounded fp32 division), stored as is (fp32) or with one round-to-nearest-even
+ *     (bf16): the Hugging Face rule, bit for bit.
+ *   no-repeat n-gram (ngram = n, 0 <= n <= 16, 0 = off): n == 1 bans every token of s; n >= 2
+ *     and L >= n: for every i in [0, L - n] with s[i + j] == s[L - n + 1 + j] for all j < n - 1,
+ *     s[i + n - 1] is banned; L < n bans nothing.
+ *   end token: ban_eos != 0 bans eos when 0 <= eos < V (a minimum length).
+ *   bad tokens: bad[0..n_bad) (int32) are banned; ids outside [0, V) are ignored.
+ * A ban stores -inf and wins over the penalty; gvl_sample and gvl_beam_step give a -inf logit
+ * probability 0.  Columns [V, ld), other rows and every logit not named above are never written.
+ * O(L + n_bad) logits touched per row; one launch (none when R == 0 or every control is off:
+ * p == 1, n == 0, ban_eos == 0, n_bad == 0), no workspace, no synchronisation.  Arguments are
+ * checked on the host before the launch (-1 and gvl_last_error naming the argument). */
+int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32, int64_t R, int64_t V,
+                       const int64_t* hist, int64_t hist_ld, int32_t n_hist, const int32_t* src,
+                       int64_t src_ld, int64_t t0, const int64_t* prompt, int64_t prompt_ld,
+                       int32_t P, int32_t rows_per_item, float rep_penalty, int32_t ngram,
+                       int32_t eos, int32_t ban_eos, const int32_t* bad, int32_t n_bad,
+                       const int32_t* flen, gvl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Small fused elementwise helpers on the hot path. */
 /* Column sums of a bf16 [rows][cols] matrix (row stride ld) -> bf16 out[cols]
