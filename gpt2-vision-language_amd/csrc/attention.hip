@@ -208,7 +208,9 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1
   const int nkt = ONE ? (nkt0 > 0 ? 1 : 0) : nkt0;
 
   // o[g][4] = row sum of the bf16 P (an MFMA against a ones fragment: the softmax
-  // denominator of exactly the P values that enter P.V, and 16 fewer VALU adds per tile)
+  // denominator of exactly the P values that enter P.V).  The log-sum-exp is not taken from
+  // it: a sum of rounded terms is off by up to 2^-8 relative, and gvl.h promises the fp32
+  // logsumexp (every backward recomputes P from it), so l[g] sums the unrounded exponentials.
   constexpr int NO = 5;
   float4_t o[G][NO];
   float m[G], l[G];
@@ -301,7 +303,7 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float e = __builtin_amdgcn_exp2f(fmaf(sc[g][n][r], p.c2, -msub));
-          if (DROP) ls += e;
+          ls += e;
           float pe = e;
           if constexpr (DROP) {
             const int64_t key = k0 + 16 * n + 4 * Gl + r;
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1
         }
       pf[g][0] = pack_frag(sc[g][0], sc[g][1]);
       if constexpr (NKS == 2) pf[g][1] = pack_frag(sc[g][NG - 2], sc[g][NG - 1]);
-      if constexpr (DROP) l[g] += ls;
+      l[g] += ls;
     }
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
@@ -336,9 +338,8 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1
   for (int g = 0; g < G; ++g) {
     float lt = l[g];
     lt = swap32_reduce<false>(swap16_reduce<false>(lt));  // lanes l, l^16, l^32, l^48 (VALU swaps)
-    if constexpr (!DROP) lt = o[g][4][0];
     if (!qok[g]) continue;
-    const float inv = 1.f / lt;
+    const float inv = 1.f / (DROP ? lt : o[g][4][0]);
     bf16_t* orow = p.o + b * p.o_sb + h * p.o_sh + q[g] * p.o_st;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -348,7 +349,6 @@ __global__ __launch_bounds__(R * 4, ONE ? (RK > R ? 5 : ATTN_ONE_BPC) : ((G == 1
     }
     if (Gl == 0 && p.lse) p.lse[(b * p.H + h) * p.Tq + q[g]] = (m[g] + log2f(lt)) * LN2;
   }
-  (void)l;
 }
 
 
@@ -887,9 +887,12 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_dma_kernel(AttnP p, AttnG g
 // pieces, source-side swizzle, counted vmcnt), instead of attn_fwd_kernel's register staging
 // one tile ahead (its timing-only build without the staging ran 18 % faster).  V is read
 // transposed by frag_tr_asm (a builtin transposed read would make hipcc drain the DMA queue).
-// Math as attn_fwd_kernel<G, false> (deferred rescale, the row sum from a ones MFMA).
+// Math as attn_fwd_kernel<G, false> (deferred rescale, the denominator of o from a ones MFMA,
+// lse from the fp32 sum of the unrounded exponentials).  Compiled for 3 waves per SIMD: left to
+// itself hipcc takes 175 VGPRs for G = 2 with the lse sum (2 waves); at 168 it spills five
+// values of the prologue that only the epilogue reads back, none inside the key loop.
 template <int G>
-__global__ __launch_bounds__(NT, 2) void attn_fwd_dma_kernel(AttnP p) {
+__global__ __launch_bounds__(NT, 3) void attn_fwd_dma_kernel(AttnP p) {
   using gvl_ring::lds_void_t;
   constexpr int QT = 64 * G, SLOT = 2 * KT * D * 2;
   __shared__ __attribute__((aligned(16))) char smem[3 * SLOT];  // [slot][K, V]
@@ -918,14 +921,16 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_dma_kernel(AttnP p) {
     if (lim < kend) kend = lim;
   }
   const int nkt = (int)((kend + KT - 1) / KT);
-  constexpr int NO = 5;  // o[g][4]: row sum of the bf16 P (ones MFMA)
+  constexpr int NO = 5;  // o[g][4]: row sum of the bf16 P (ones MFMA), the denominator of o
   float4_t o[G][NO];
   float m[G];
+  float l[G];  // fp32 sum of the unrounded exponentials, for lse (as attn_fwd_kernel's l)
 #pragma unroll
   for (int g = 0; g < G; ++g) {
 #pragma unroll
     for (int t = 0; t < NO; ++t) o[g][t] = float4_t{0.f, 0.f, 0.f, 0.f};
     m[g] = -INFINITY;
+    l[g] = 0.f;
   }
   short8_t ones;
 #pragma unroll
@@ -1015,12 +1020,17 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_dma_kernel(AttnP p) {
         m[g] = mnew;
 #pragma unroll
         for (int t = 0; t < NO; ++t) o[g][t] *= alpha;
+        l[g] *= alpha;
       }
       const float msub = (m[g] == -INFINITY) ? 0.f : m[g];
 #pragma unroll
-      for (int n = 0; n < 4; ++n)
+      for (int n = 0; n < 4; ++n) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sc[g][n][r] = __builtin_amdgcn_exp2f(fmaf(sc[g][n][r], p.c2, -msub));
+        for (int r = 0; r < 4; ++r) {
+          sc[g][n][r] = __builtin_amdgcn_exp2f(fmaf(sc[g][n][r], p.c2, -msub));
+          l[g] += sc[g][n][r];
+        }
+      }
       pf[g][0] = pack_frag(sc[g][0], sc[g][1]);
       pf[g][1] = pack_frag(sc[g][2], sc[g][3]);
     }
@@ -1057,9 +1067,10 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_dma_kernel(AttnP p) {
   for (; kt < nkt; ++kt) tile(kt, std::true_type{});
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    const float lt = o[g][4][0];
+    float lt = l[g];
+    lt = swap32_reduce<false>(swap16_reduce<false>(lt));  // the row's lanes l, l^16, l^32, l^48
     if (!qok[g]) continue;
-    const float inv = 1.f / lt;
+    const float inv = 1.f / o[g][4][0];
     bf16_t* orow = p.o + b * p.o_sb + h * p.o_sh + q[g] * p.o_st;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -170,6 +170,51 @@ def assert_f32_close(got, ref64, scale, slack, name=""):
     return err_units(got, ref64, scale)
 
 
+BF16_UNIT = 2.0 ** -8  # the largest relative error of one bf16 rounding
+# Below the smallest normal (2**-126, bf16 and fp32 alike) a rounding is no longer relative and
+# the GPU may flush a term to zero: an absolute 2**-126 per term, for the at most 2**10 terms of
+# at most 2**4 that the attention tests sum.  Nothing above 1e-33 is affected.
+ATTN_FLUSH = 2.0 ** -112
+
+
+def attn_units(got, ref64, E):
+    """max |got - ref64| in units of 2**-8 * E (E: the per-element sum of the absolute values of
+    the terms added to form the result, tests/attn_ref.py)."""
+    err = np.abs(f64(got) - f64(ref64))
+    unit = BF16_UNIT * np.abs(f64(E))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(unit > 0, err / unit, np.where(err == 0, 0.0, np.inf))
+    r = np.where(np.isnan(r) | (err <= ATTN_FLUSH), np.where(np.isnan(err), np.inf, 0.0), r)
+    return float(r.max()) if r.size else 0.0
+
+
+def assert_attn_close(got_bf16, ref64, E, units, name="", slack=0):
+    """Every element of the bf16 attention output within units * 2**-8 * E (+ slack * 2**-24 * E
+    for the fp32 arithmetic) of the float64 reference: `units` counts the bf16 roundings on the
+    way to the element, each at most 2**-8 of the terms it rounds.  A NaN or an infinity fails.
+    Returns the worst error in units of 2**-8 * E; on failure reports the worst element."""
+    e = np.abs(f64(E))
+    unit = np.maximum(BF16_UNIT * e, 2.0 ** -149)
+    _close(got_bf16, ref64, (units * BF16_UNIT + slack * F32_UNIT) * e + ATTN_FLUSH, unit,
+           name or "attn")
+    return attn_units(got_bf16, ref64, E)
+
+
+def assert_attn_tight(got_bf16, ref64, E, emu64, name="", slack=0, margin=4):
+    """The bound the reference sets for itself: every element within margin x the worst error of
+    the bf16-rounding emulation `emu64` (in units of 2**-8 * E, over the whole tensor) of the
+    float64 reference, + slack * 2**-24 * E.  margin = 4 is what the row-wise tests give an fp32
+    evaluation in another order; here it covers another accumulation order and rounding points
+    that fall differently.  Returns (the result's worst error, the emulation's) in those units."""
+    r_emu = attn_units(emu64, ref64, E)
+    assert np.isfinite(r_emu), f"{name}: the emulation itself is off where E = 0"
+    e = np.abs(f64(E))
+    unit = np.maximum(BF16_UNIT * e, 2.0 ** -149)
+    _close(got_bf16, ref64, (margin * r_emu * BF16_UNIT + slack * F32_UNIT) * e + ATTN_FLUSH, unit,
+           name or "attn tight")
+    return attn_units(got_bf16, ref64, E), r_emu
+
+
 def check_summary(fx, name, t, rtol):
     """Compare tensor t against the fixture summary of `name` (full or sampled + sums)."""
     a = t.detach().to(torch.float64).cpu().numpy().reshape(-1)
