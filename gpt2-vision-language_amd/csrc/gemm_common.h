@@ -482,7 +482,9 @@ GVL_DEV bool gemm_splitk_arrive(const GemmP& p, const float4_t (&acc)[FM][FN], i
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int soff = __builtin_amdgcn_readfirstlane((int)((base + (int64_t)i * 16 * p.N + j * 16) * 4));
-      if (mok && nw0 + j * 16 < p.N)
+      // per lane, not per fragment: with N % 16 == 8 the last fragment's upper two column quads
+      // lie past N, i.e. on the next row's first 8 columns of the [M][N] slab (another tile's)
+      if (mok && nw0 + j * 16 + 4 * (lane >> 4) < p.N)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[i][j]), rw, voff,
                                                soff, 16);
     }

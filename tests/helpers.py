@@ -162,6 +162,20 @@ def assert_bf16_close(got, ref64, *, scale=None, slack=0, name=""):
     return _close(got, ref64, tol, ulp, name or "bf16")
 
 
+def assert_bf16_rounded(got, ref64, scale, slack, name=""):
+    """Every element of the bf16 result `got` within ulp_bf16(ref64) / 2 + slack * 2**-24 * scale
+    of the float64 reference: the correct rounding (to nearest) of a value that fp32 arithmetic
+    may have moved by `slack` units of 2**-24 * scale before it was rounded.  Unlike
+    assert_bf16_close there is no second half ulp for a flipped near-tie: `slack`, taken from an
+    fp32 evaluation of the reference itself, is what may flip it, so truncation (up to one ulp)
+    fails.  The ulp is that of the reference's binade, so just below a power of two, where the
+    value may round up into the next binade, the bound is the tighter of the two.  Returns the
+    worst error in ulps; on failure reports the worst element."""
+    ulp = ulp_bf16(ref64)
+    tol = 0.5 * ulp + slack * F32_UNIT * np.abs(f64(scale))
+    return _close(got, ref64, tol, ulp, name or "bf16 rounded")
+
+
 def assert_f32_close(got, ref64, scale, slack, name=""):
     """Every element of the fp32 result `got` within slack * 2**-24 * scale of the float64
     reference (no ulp term).  Returns the measured error in those units."""

@@ -1,8 +1,10 @@
 """Per-element parity of the row-wise and element-wise kernels on the MI355X.
 
-tests/helpers.py::rel_err divides by the largest element of the whole tensor, which suits GEMM
-outputs and hides almost everything in outputs that span orders of magnitude (AdamW state,
-softmax gradients, LayerNorm rows of different scale).  Here every element is compared with a
+tests/helpers.py::rel_err divides by the largest element of the whole tensor, which hides almost
+everything in outputs that span orders of magnitude (AdamW state, softmax gradients, LayerNorm
+rows of different scale) and, in a GEMM output, a truncating final rounding, bf16 split-K
+partials and wrong rows or columns of small scale (tests/test_gemm_ref_cpu.py; the GEMMs are
+held per element by tests/test_gpu_gemm.py).  Here every element is compared with a
 float64 CPU reference that reads the same bf16 / fp32 inputs as the kernel, one step from given
 inputs: bf16 outputs to one bf16 ulp (helpers.assert_bf16_close), fp32 outputs to a count of
 fp32 roundings (helpers.assert_f32_close) taken from the same formula in fp32 torch on the CPU
