@@ -166,6 +166,7 @@ __global__ __launch_bounds__(SMP_NT) void sample_kernel(SampP p) {
   __shared__ uint32_t hist[256];
   __shared__ float histf[256];
   __shared__ uint32_t sel[2];
+  __shared__ int owner;
   __shared__ float c_above;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
@@ -275,26 +276,33 @@ __global__ __launch_bounds__(SMP_NT) void sample_kernel(SampP p) {
   if (tid == 0) {
     sel[0] = 0xFFFFFFFFu;  // drawn index
     sel[1] = 0;            // fallback: the highest-index kept token (target rounded to tot)
+    owner = -1;
   }
   __syncthreads();
+  // The owner of target is the LAST thread with kept mass and pre <= target: the first such
+  // thread has pre == 0, so these intervals tile [0, tot) whatever the rounding of the scan.
+  // (pre <= target < pre + s per thread does not: fl(pre_i + s_i) != pre_{i+1}, and a target
+  // in the gap between them was claimed by nobody and drew the fallback.)
   if (s > 0.f) {
     atomicMax(&sel[1], (uint32_t)(i0 + last));
-    if (pre <= target && target < pre + s) {
-      float acc = pre;
-      int pick = last;
-      bool found = false;
+    if (pre <= target && target < tot) atomicMax(&owner, tid);
+  }
+  __syncthreads();
+  if (tid == owner) {
+    float acc = pre;
+    int pick = last;  // acc never passes target (rounding): my last kept element
+    bool found = false;
 #pragma unroll
-      for (int j = 0; j < SMP_E; ++j) {
-        if (!found && x[j] > 0.f) {
-          acc += x[j];
-          if (acc > target) {
-            pick = j;
-            found = true;
-          }
+    for (int j = 0; j < SMP_E; ++j) {
+      if (!found && x[j] > 0.f) {
+        acc += x[j];
+        if (acc > target) {
+          pick = j;
+          found = true;
         }
       }
-      atomicMin(&sel[0], (uint32_t)(i0 + pick));
     }
+    sel[0] = (uint32_t)(i0 + pick);
   }
   __syncthreads();
   if (tid == 0) p.out[row] = (int64_t)(sel[0] != 0xFFFFFFFFu ? sel[0] : sel[1]);

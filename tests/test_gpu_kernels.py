@@ -1258,18 +1258,33 @@ def test_embedding_fwd_bwd(cuda):
     assert rel_err(ape.cpu().numpy(), pr.grad.numpy()) < 1e-5
 
 
-@pytest.mark.parametrize("case", ["small", "lm", "hot", "chunks"])
+_EMB_DET = {"small": (300, 128, 3, 20, 4), "lm": (50304, 768, 16, 1024, 0),
+            "hot": (1000, 256, 5, 700, 2), "chunks": (4000, 64, 9, 4000, 1),
+            # the width limits: one lane group, a partly used second slice, the maximum
+            "c8-n1024": (50, 8, 4, 256, 1), "c520-g5": (40, 520, 5, 7, 2), "c1024": (40, 1024, 1, 9, 0),
+            # token counts at the sort tile (1024) and chunk (16384) edges, G = 1 for dwpe
+            "n1025-g1": (50, 8, 1, 1025, 0), "n16384": (300, 8, 4, 4096, 1), "n16385": (300, 8, 1, 16385, 0),
+            "t1": (30, 64, 37, 1, 3),
+            # the largest legal id: V = 2**18 - 2
+            "maxid": ((1 << 18) - 2, 8, 4, 64, 0)}
+
+
+@pytest.mark.parametrize("case", list(_EMB_DET))
 def test_embedding_bwd_det_bit_exact(cuda, case):
     """gvl_embedding_bwd_det: per-id fp32 sums in token order, one bf16 update per row —
     emulated exactly on the host (np.add.at applies its updates in index order), so the
     result must match BIT FOR BIT, including hot ids (one id repeated thousands of times),
     out-of-range ids (skipped), a token count that is not a whole number of sort tiles and
-    inputs longer than one 16,384-token chunk (chunks applied in order)."""
+    inputs longer than one 16,384-token chunk (chunks applied in order); C = 8, 520 and the
+    limit 1024; 1024 / 1025 / 16384 / 16385 tokens; T = 1; the largest legal id at
+    V = 2**18 - 2; dwpe over G = 1, 4 and 5 groups (the four-row load group and its tail)."""
     K_ = _k()
-    V, C, G, T, M = {"small": (300, 128, 3, 20, 4), "lm": (50304, 768, 16, 1024, 0),
-                     "hot": (1000, 256, 5, 700, 2), "chunks": (4000, 64, 9, 4000, 1)}[case]
+    V, C, G, T, M = _EMB_DET[case]
     gen = torch.Generator().manual_seed(11)
     idx = torch.randint(0, V, (G, T), generator=gen)
+    if case == "maxid":
+        idx[0, 0] = idx[3, 63] = idx[1, 7] = V - 1
+        idx[2, 5] = 0
     if case == "hot":
         idx[:, ::2] = 7          # 1,750 copies of id 7, interleaved
         idx[1, 5] = V + 3        # out of range: contributes nothing
