@@ -124,6 +124,10 @@ SIGNATURES = {
     "gvl_logits_process": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp,
                                      c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_f32, c_i32, c_i32,
                                      c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "gvl_token_logprobs": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp]),
+    "gvl_sequence_score": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp]),
     "gvl_colsum_workspace_size": (c_i64, [c_i64, c_i64]),
     "gvl_colsum": (C.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "gvl_colsum_batched_workspace_size": (c_i64, [c_i32, c_i64, c_i64]),

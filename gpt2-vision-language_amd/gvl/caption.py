@@ -182,7 +182,9 @@ class GPT_Caption(nn.Module):
         x = self.gpt.decode(full_embeds)
         return Fn.lm_logits(x, bf(self.gpt.lm_head.weight))
 
-    def forward(self, patch_tokens, input_ids, labels=None):
+    def hidden(self, patch_tokens, input_ids):
+        """(final-LayerNorm hidden states [B, M + T, C] that forward feeds the lm_head, M = the
+        number of bridge tokens in front, T = the text length kept by the block_size cut)."""
         B, T_txt = input_ids.shape
         if patch_tokens.dim() == 2:
             patch_tokens = patch_tokens.unsqueeze(1)
@@ -191,13 +193,15 @@ class GPT_Caption(nn.Module):
         img = self.bridge(x_img)
         M = img.size(1)
         if M + T_txt > self.block_size:
-            cut = self.block_size - M
-            input_ids = input_ids[:, :cut]
-            if labels is not None:
-                labels = labels[:, :cut]
-            T_txt = cut
+            T_txt = self.block_size - M
+            input_ids = input_ids[:, :T_txt]
         full = Fn.EmbedFn.apply(input_ids, bf(self.wte.weight), bf(self.wpe.weight), img)
-        x = self.gpt.decode(full)
+        return self.gpt.decode(full), M, T_txt
+
+    def forward(self, patch_tokens, input_ids, labels=None):
+        x, M, T_txt = self.hidden(patch_tokens, input_ids)
+        if labels is not None and T_txt < input_ids.shape[1]:
+            labels = labels[:, :T_txt]
         w = bf(self.gpt.lm_head.weight)
         if labels is None:
             return Fn.lm_logits(x, w), None

@@ -164,7 +164,8 @@ class GPT(nn.Module):
             blk.xattn.kv_proj.weight._gvl_stack_key = "xattn.kv_proj.weight"
             blk.xattn.kv_proj.bias._gvl_stack_key = "xattn.kv_proj.bias"
 
-    def forward(self, idx, z=None, targets=None, target_mask=None):
+    def hidden(self, idx, z=None):
+        """The final-LayerNorm hidden states [B, T, C] that forward feeds the lm_head."""
         B, T = idx.size()
         if T > self.config.block_size:
             raise AssertionError(f"Cannot forward sequence of length {T}, block size is only "
@@ -180,7 +181,10 @@ class GPT(nn.Module):
                 kv = Fn.CrossKVFn.apply(zp, slab, *wb)
         for i, blk in enumerate(tr.h):
             x = blk(x, zp, None if kv is None else (kv, i, slab))
-        x = Fn.LayerNormFn.apply(x, bf(tr.ln_f.weight), bf(tr.ln_f.bias), 1e-5)
+        return Fn.LayerNormFn.apply(x, bf(tr.ln_f.weight), bf(tr.ln_f.bias), 1e-5)
+
+    def forward(self, idx, z=None, targets=None, target_mask=None):
+        x = self.hidden(idx, z)
         w = bf(self.lm_head.weight)
         if targets is None:
             return Fn.lm_logits(x, w), None

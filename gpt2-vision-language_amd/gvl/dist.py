@@ -339,3 +339,15 @@ def all_reduce_mean_(t, group=None):
     if dist.is_initialized() and dist.get_world_size(group) > 1:
         _avg(t, group, async_op=False)
     return t
+
+
+def all_reduce_sum_(t, group=None):
+    """The HellaSwag count all-reduce (train_gpt2.py:410-416): SUM over the group, in place."""
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        gloo_gpu = t.is_cuda and not _is_nccl(group)  # see _avg: gloo is not stream-ordered
+        if gloo_gpu:
+            torch.cuda.synchronize(t.device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        if gloo_gpu:
+            torch.cuda.synchronize(t.device)
+    return t

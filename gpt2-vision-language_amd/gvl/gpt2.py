@@ -172,7 +172,9 @@ class GPT(nn.Module):
         self.lm_head.weight._gvl_tied = True
         self.apply(lambda m: init_gpt_weights(m, self.config.n_layer))
 
-    def forward(self, idx, targets=None):
+    def hidden(self, idx):
+        """The final-LayerNorm hidden states [B, T, C] that forward feeds the lm_head (gvl.score
+        runs the lm_head on the rows it scores only)."""
         B, T = idx.size()
         if T > self.config.block_size:
             raise AssertionError(f"Cannot forward sequence of length {T}, block size is only "
@@ -181,7 +183,10 @@ class GPT(nn.Module):
         x = Fn.EmbedFn.apply(idx, bf(tr.wte.weight), bf(tr.wpe.weight), None)
         for blk in tr.h:
             x = blk(x)
-        x = Fn.LayerNormFn.apply(x, bf(tr.ln_f.weight), bf(tr.ln_f.bias), 1e-5)
+        return Fn.LayerNormFn.apply(x, bf(tr.ln_f.weight), bf(tr.ln_f.bias), 1e-5)
+
+    def forward(self, idx, targets=None):
+        x = self.hidden(idx)
         if targets is None:
             logits = Fn.lm_logits(x, bf(self.lm_head.weight))
             return logits, None

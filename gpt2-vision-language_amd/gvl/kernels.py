@@ -595,6 +595,93 @@ def sample(logits2, u, temperature=1.0, top_k=0, top_p=1.0, out=None):
     return out
 
 
+def _score_out(t, n, dtype, device, name):
+    """An optional output of the scoring launchers: True allocates it, None / False leaves it
+    out, a tensor (contiguous, n elements of dtype) is written."""
+    if t is None or t is False:
+        return None
+    if t is True:
+        return torch.empty(n, dtype=dtype, device=device)
+    _dev(t)
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"gvl: {name} must be a contiguous {dtype} tensor of {n} elements")
+    return t
+
+
+def _score_mask(mask, n):
+    if mask is None:
+        return None
+    _dev(mask)
+    mk = mask.reshape(-1)
+    if mk.dtype != torch.uint8:
+        mk = mk.to(torch.uint8)
+    if mk.numel() != n:
+        raise ValueError(f"gvl: mask must have {n} elements")
+    return mk.contiguous()
+
+
+def token_logprobs(logits2, targets, mask=None, *, vocab=None, logp=True, lse=True, argmax=True,
+                   rank=True):
+    """Per row of logits2 [rows, >= V] bf16 / fp32 and its target (include/gvl.h
+    gvl_token_logprobs): logp = x[t] - lse, lse, argmax (first maximum) and the target's rank (0:
+    it is the argmax).  targets int64 [rows] (-100: skipped); mask [rows], 0: skipped; `vocab` <
+    logits2.shape[1] marks the trailing columns as padding.  Each output: True allocates it, None
+    leaves it out, a tensor is written in place.  -> (logp fp32, lse fp32, argmax int32, rank
+    int32), None where left out."""
+    _dev(logits2, targets)
+    _rowmajor(logits2, "logits")
+    if logits2.dtype not in (BF16, F32):
+        raise ValueError("gvl: token_logprobs takes bf16 or fp32 logits")
+    rows = logits2.shape[0]
+    V = logits2.shape[1] if vocab is None else int(vocab)
+    if V > logits2.shape[1]:
+        raise ValueError(f"gvl: vocab = {V} exceeds the {logits2.shape[1]} logits columns")
+    tg = targets.reshape(-1)
+    if tg.dtype != torch.int64:
+        tg = tg.long()
+    tg = tg.contiguous()
+    if tg.numel() != rows:
+        raise ValueError(f"gvl: {tg.numel()} targets for {rows} logits rows")
+    mk = _score_mask(mask, rows)
+    dev = logits2.device
+    logp = _score_out(logp, rows, F32, dev, "logp")
+    lse = _score_out(lse, rows, F32, dev, "lse")
+    argmax = _score_out(argmax, rows, torch.int32, dev, "argmax")
+    rank = _score_out(rank, rows, torch.int32, dev, "rank")
+    _lib.check(_L().gvl_token_logprobs(logits2.data_ptr(), logits2.stride(0),
+                                       int(logits2.dtype == F32), rows, V, tg.data_ptr(), _p(mk),
+                                       _p(logp), _p(lse), _p(argmax), _p(rank), _stream()),
+               "gvl_token_logprobs")
+    return logp, lse, argmax, rank
+
+
+def sequence_score(logp, mask=None, group=1):
+    """Per-sequence and per-example reduction of token log-probabilities (include/gvl.h
+    gvl_sequence_score).  logp fp32 [N, T]; mask [N, T] of 0 / 1 (None: every position counts);
+    `group` consecutive sequences form an example.  -> (sum_nll fp32 [N], count int32 [N],
+    mean_nll fp32 [N], pred_norm int32 [N / group], pred int32 [N / group])."""
+    _dev(logp)
+    if logp.dim() != 2 or logp.dtype != F32:
+        raise ValueError("gvl: sequence_score takes fp32 logp [N, T]")
+    logp = logp.contiguous()
+    N, T = logp.shape
+    group = int(group)
+    if group < 1 or N % group:
+        raise ValueError(f"gvl: group = {group} does not divide the {N} sequences")
+    mk = _score_mask(mask, N * T)
+    dev = logp.device
+    i32 = torch.int32
+    out = (torch.empty(N, dtype=F32, device=dev), torch.empty(N, dtype=i32, device=dev),
+           torch.empty(N, dtype=F32, device=dev), torch.empty(N // group, dtype=i32, device=dev),
+           torch.empty(N // group, dtype=i32, device=dev))
+    if N == 0:
+        return out
+    _lib.check(_L().gvl_sequence_score(logp.data_ptr(), _p(mk), N, T, group,
+                                       *[t.data_ptr() for t in out], _stream()),
+               "gvl_sequence_score")
+    return out
+
+
 # ---------------------------------------------------------------------- cross entropy
 def cross_entropy(logits2, targets, *, rows_per_group=None, group_stride=0, row_offset=0,
                   mask=None, mask_mode=False, want_grad=True, vocab=None, dlogits=None):

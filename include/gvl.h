@@ -419,6 +419,42 @@ int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32, int64_t R,
                        int32_t eos, int32_t ban_eos, const int32_t* bad, int32_t n_bad,
                        const int32_t* flen, gvl_stream_t stream);
 
+/* Scoring of given tokens (the HellaSwag evaluation of train_gpt2.py:190-202, 394-426, caption
+ * reranking, perplexity).  Added at ABI v14 without a version bump, like the beam and logits
+ * entry points: new symbols, nothing existing changes.
+ *
+ * gvl_token_logprobs: per row r of logits [rows, V] bf16 or fp32 (row stride ld >= V in elements,
+ * 1 <= V <= 65536, V any value; columns [V, ld) never count as logits; rows whose address and
+ * stride are 16-byte aligned are read with 16-byte loads, others element by element) and its
+ * target t = targets[r] (int64), in fp32:
+ *   lse[r]    = max + log(sum_v exp(x[v] - max));
+ *   logp[r]   = x[t] - lse[r];
+ *   argmax[r] = the lowest v with x[v] == max (torch.argmax's tie-break), int32;
+ *   rank[r]   = #{v: x[v] > x[t]} + #{v < t: x[v] == x[t]}, int32: 0 iff t is the argmax.
+ * Each of the four outputs may be null.  mask: optional uint8 [rows].
+ *   skipped: a row with t == -100 or mask[r] == 0; its logits are not read; logp = 0, lse = 0,
+ *     argmax = -1, rank = -1.
+ *   t outside [0, V) and not -100: nothing outside the row is read; logp = NaN, rank = -1 (the
+ *     convention of gvl_cross_entropy); lse and argmax are the row's.
+ *   x[t] = -inf in a row with a finite maximum (a banned token): logp = -inf exactly.
+ * One launch, one workgroup per row, no workspace, no synchronisation.
+ *
+ * gvl_sequence_score: logp fp32 [N, T] (row-major, as written by gvl_token_logprobs), mask
+ * optional uint8 [N, T], group in 1..16 dividing N.  Per sequence n, over the positions with
+ * mask != 0 (all without a mask): sum_nll[n] = sum of -logp in fp32 in a fixed order, count[n]
+ * (int32), mean_nll[n] = sum_nll / count (0 / 0 = NaN).  Per example g = `group` consecutive
+ * sequences: pred_norm[g] = the first argmin of mean_nll, pred[g] = the first argmin of sum_nll
+ * (int32, index within the example); both -1 when a sequence of the example has count 0.
+ * One launch, one workgroup per example, no workspace, no synchronisation.
+ * Both check their arguments on the host before the launch (-1 and gvl_last_error naming the
+ * argument). */
+int gvl_token_logprobs(const void* logits, int64_t ld, int32_t logits_fp32, int64_t rows,
+                       int64_t V, const int64_t* targets, const uint8_t* mask, float* logp,
+                       float* lse, int32_t* argmax, int32_t* rank, gvl_stream_t stream);
+int gvl_sequence_score(const float* logp, const uint8_t* mask, int64_t N, int64_t T,
+                       int32_t group, float* sum_nll, int32_t* count, float* mean_nll,
+                       int32_t* pred_norm, int32_t* pred, gvl_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Small fused elementwise helpers on the hot path. */
 /* Column sums of a bf16 [rows][cols] matrix (row stride ld) -> bf16 out[cols]
