@@ -1330,48 +1330,7 @@ int fill(const gvl_attn_desc* d, AttnP& p) {
 
 // Two query groups per wave (128-row blocks) only pay off once a block has enough rows;
 // the short caption sequences (31-64 rows) keep 64-row blocks.
-// GVL_ATTN_G=1 keeps 64-row blocks everywhere (A/B of occupancy against rows per block).
-int pick_groups(int64_t T) {
-  static const int forced = gvl::env_int("GVL_ATTN_G", 0);
-  if (forced == 1) return 1;
-  return T > 64 ? 2 : 1;
-}
-
-// Single-launch backward for Tq, Tk <= 64 (attn_bwd_short_kernel); GVL_ATTN_SHORT=0 restores the
-// three-kernel path (A/B measurement).
-bool short_bwd_enabled() {
-  static const bool on = gvl::env_on("GVL_ATTN_SHORT");
-  return on;
-}
-
-// LDS-DMA forward (attn_fwd_dma_kernel) for multi-tile key ranges without dropout;
-// GVL_ATTN_FWD_DMA=0: the register-staged attn_fwd_kernel (A/B).
-bool fwd_dma_enabled() {
-  static const bool on = gvl::env_on("GVL_ATTN_FWD_DMA");
-  return on;
-}
-
-// 32-row short backward (attn_bwd_short_kernel<*, 32>) for Tq, Tk <= 32; GVL_ATTN_SHORT32=0: the
-// 64-row kernel (A/B).
-bool short32_enabled() {
-  static const bool on = gvl::env_on("GVL_ATTN_SHORT32");
-  return on;
-}
-
-// 32-query tiles over a 64-key tile (attn_fwd_kernel<1, *, true, 32, 64>, attn_bwd_short_kernel<*, 32,
-// 64>) for Tq <= 32 < Tk <= 64 (the cross-attention over 33 image tokens); GVL_ATTN_SHORT3264=0:
-// the 64-row kernels (A/B).
-bool short3264_enabled() {
-  static const bool on = gvl::env_on("GVL_ATTN_SHORT3264");
-  return on;
-}
-
-// One-tile forward (attn_fwd_kernel<1, *, true>) for Tk <= 64; GVL_ATTN_FWD_ONE=0: the two-stage
-// kernel (A/B).
-bool fwd_one_enabled() {
-  static const bool on = gvl::env_on("GVL_ATTN_FWD_ONE");
-  return on;
-}
+int pick_groups(int64_t T) { return T > 64 ? 2 : 1; }
 
 // launch(std::bool_constant<DROP>{}) for DROP = has_drop: a route names its kernel once and both
 // dropout instances are built.
@@ -1392,31 +1351,31 @@ extern "C" int gvl_attn_fwd(const gvl_attn_desc* d, gvl_stream_t stream) {
   const int G = pick_groups(d->Tq);
   dim3 grid(grid_1d(d, (d->Tq + 64 * G - 1) / (64 * G)));
   hipStream_t s = gvl::as_stream(stream);
-  if (!p.has_drop && d->Tk > KT && fwd_dma_enabled()) {
+  // (tests/attn_ref.py::routes restates this ladder and the backward's, branch for branch)
+  if (!p.has_drop && d->Tk > KT) {  // LDS-DMA forward: no dropout, more than one 64-key tile
     if (G == 2) gvl::launch_timed(attn_fwd_dma_kernel<2>, grid, dim3(NT), 0, s, p);
     else gvl::launch_timed(attn_fwd_dma_kernel<1>, grid, dim3(NT), 0, s, p);
   } else if (G == 2) {
     by_drop(p, [&](auto drop) {
       gvl::launch_timed(attn_fwd_kernel<2, drop()>, grid, dim3(NT), 0, s, p);
     });
-  } else if (d->Tq <= 32 && d->Tk <= 32 && fwd_one_enabled() && short32_enabled()) {
+  } else if (d->Tq <= 32 && d->Tk <= 32) {  // one-tile forwards: 32 rows (2 waves),
     dim3 g32(grid_1d(d, 1));
     by_drop(p, [&](auto drop) {
       gvl::launch_timed(attn_fwd_kernel<1, drop(), true, 32>, g32, dim3(128), 0, s, p);
     });
-  } else if (d->Tq <= 32 && d->Tk <= KT && fwd_one_enabled() && short32_enabled() && short3264_enabled()) {
+  } else if (d->Tq <= 32 && d->Tk <= KT) {  // 32 queries over 64 keys (33 image tokens),
     dim3 g32(grid_1d(d, 1));
     by_drop(p, [&](auto drop) {
       gvl::launch_timed(attn_fwd_kernel<1, drop(), true, 32, 64>, g32, dim3(128), 0, s, p);
     });
-  } else if (d->Tk <= KT && fwd_one_enabled()) {
+  } else if (d->Tk <= KT) {  // 64 rows
     by_drop(p, [&](auto drop) {
       gvl::launch_timed(attn_fwd_kernel<1, drop(), true>, grid, dim3(NT), 0, s, p);
     });
   } else {
-    by_drop(p, [&](auto drop) {
-      gvl::launch_timed(attn_fwd_kernel<1, drop()>, grid, dim3(NT), 0, s, p);
-    });
+    // Tk > 64 got past the first branch, so there is dropout: only that instance is built
+    gvl::launch_timed(attn_fwd_kernel<1, true>, grid, dim3(NT), 0, s, p);
   }
   GVL_LAUNCH_CHECK("gvl_attn_fwd");
   return 0;
@@ -1447,13 +1406,13 @@ extern "C" int gvl_attn_bwd(const gvl_attn_desc* d, const gvl_attn_bwd_desc* gd,
   g.Dws = static_cast<float*>(gd->workspace);
   g.Lws = g.Dws + d->B * d->H * d->Tq;
   hipStream_t s = gvl::as_stream(stream);
-  if (d->Tq <= 64 && d->Tk <= 64 && short_bwd_enabled()) {
+  if (d->Tq <= 64 && d->Tk <= 64) {  // single-launch backward
     dim3 grid((unsigned)(d->B * d->H));
-    if (d->Tq <= 32 && d->Tk <= 32 && short32_enabled()) {
+    if (d->Tq <= 32 && d->Tk <= 32) {
       by_drop(p, [&](auto drop) {
         gvl::launch_timed(attn_bwd_short_kernel<drop(), 32>, grid, dim3(128), 0, s, p, g);
       });
-    } else if (d->Tq <= 32 && short32_enabled() && short3264_enabled()) {
+    } else if (d->Tq <= 32) {
       by_drop(p, [&](auto drop) {
         gvl::launch_timed(attn_bwd_short_kernel<drop(), 32, 64>, grid, dim3(128), 0, s, p, g);
       });

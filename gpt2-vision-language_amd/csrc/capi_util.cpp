@@ -34,16 +34,6 @@ int num_cus() {
   return cached[dev];
 }
 
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-bool env_on(const char* name) {
-  const char* e = getenv(name);
-  return !(e && e[0] == '0');
-}
-
 bool take_launch_events(hipEvent_t* start, hipEvent_t* stop) {
   if (!g_ev_start || !g_ev_stop) return false;
   *start = g_ev_start;

@@ -10,10 +10,6 @@ namespace gvl {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 int num_cus();  // compute units of the current device (cached per device)
-// Environment knobs of the host code (`static const int v = env_int(...)`: read once per site):
-// atoi of the variable, `dflt` when it is unset; env_on: on unless the value starts with '0'.
-int env_int(const char* name, int dflt);
-bool env_on(const char* name);
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

@@ -148,22 +148,13 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(GemmP p) {
   gemm_epilogue<4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
-// GVL_GEMM_IMPL=regstage|lds|ring|pp picks the kernel family (0|1|2|3, default 3: the
-// four-wave kernels for narrow outputs, the persistent ping-pong kernel where it fills the
-// chip, else the 128x128 ring); GVL_GEMM_CFG forces a tile config of that family (impl 3:
-// 3 = the persistent kernel, 10 = the four-wave kernel, 11 = the default routing without it).
+// What gvl_gemm_tune writes.  impl picks the kernel family (0 register-staged, 1 lds, 2 ring,
+// 3 the default: the four-wave kernels for narrow outputs, the persistent ping-pong kernel
+// where it fills the chip, else the 128x128 ring); cfg forces a tile config of that family
+// (impl 3: 3 = the persistent kernel, 10 = the four-wave kernel, 11 = the default routing
+// without it).
 struct GemmEnv {
-  int impl = 3, cfg = -1, group = 0;  // group 0: by shape (gemm_group)
-  GemmEnv() {
-    const int gr = gvl::env_int("GVL_GEMM_GROUP", 0);
-    if (gr > 0) group = gr;
-    const char* s = getenv("GVL_GEMM_IMPL");
-    if (s && s[0] == 'r' && s[1] == 'e') impl = 0;
-    if (s && s[0] == 'l') impl = 1;
-    if (s && s[0] == 'r' && s[1] == 'i') impl = 2;
-    if (s && s[0] == 'p') impl = 3;
-    cfg = gvl::env_int("GVL_GEMM_CFG", -1);
-  }
+  int impl = 3, cfg = -1;
 };
 GemmEnv& env() {
   static GemmEnv e;
@@ -173,10 +164,8 @@ GemmEnv& env() {
 // Tile rows per L2 group of the tile walk (gemm_tile_of): 4 for M or K >= 12288 (the LM's
 // 16384-token GEMMs and its weight gradients over 16384 tokens), else 8.  Measured against 8
 // everywhere and against 4 for M >= 12288 only: LM step 856k -> 862k tokens/s, Q-Former
-// unchanged (profiles/r3/gemm_walk_group_ab_r3s2.txt).  GVL_GEMM_GROUP=n overrides it for
-// every GEMM.
+// unchanged (profiles/r3/gemm_walk_group_ab_r3s2.txt).
 int gemm_group(const gvl_gemm_desc* d) {
-  if (env().group > 0) return env().group;
   if (d->m >= 12288 || d->k >= 12288) return 4;
   return 8;
 }
@@ -232,7 +221,7 @@ extern "C" int gvl_gemm_tune(int32_t impl, int32_t cfg) {
   return 0;
 }
 
-// The routing, once: family by gvl_gemm_tune / GVL_GEMM_IMPL and shape, the family's planner,
+// The routing, once: family by gvl_gemm_tune and shape, the family's planner,
 // its launcher down to the leaf, which launches or names its kernel as the sink asks
 // (gemm_common.h).  Returns the family's label for the launch check.
 static const char* gemm_dispatch(const gvl_gemm_desc* d, const gvl::GemmSink& k) {
@@ -401,8 +390,7 @@ static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t
     // gradients (768 x 768, K = 16384) are 144 tiles of 256 x 192 on 256 CUs; split, 216
     // half-K 256 x 256 items.  Estimate as in the planner (gemm_plan.hip): rounds x (32-deep
     // K-steps + 6), a 192-wide step counted 0.75 / 0.9, ~4 for the combine; required >= 10 %
-    // better.  GVL_BATCHED_SPLIT=0 turns it off (A/B).
-    static const bool split_on = gvl::env_on("GVL_BATCHED_SPLIT");
+    // better.
     const int64_t tn256 = (p.N + 255) / 256, items2 = 2 * (int64_t)count * tm * tn256;
     const int64_t need = (int64_t)count * 2 * p.M * p.N * 4;
     // a split batch's bias gradients go to gvl_colsum_batched after the GEMM: every one of its
@@ -412,7 +400,7 @@ static int gemm_batched_impl(const gvl_gemm_desc* d, void* const* dbias, int32_t
                      p.M % 8 == 0 && d[0].lda % 8 == 0;
     for (int i = 0; dbias && colsum_ok && i < count; ++i)
       colsum_ok = dbias[i] != nullptr && gvl::aligned16(d[i].a);
-    if (split_on && ws && tickets && p.K % 64 == 0 && p.K / 2 >= 256 &&
+    if (ws && tickets && p.K % 64 == 0 && p.K / 2 >= 256 &&
         (int64_t)count * tm * tn256 * 8 <= nticket && need <= ws_bytes && (!dbias || colsum_ok)) {
       auto est = [&](int64_t items, double steps, double w) {
         return (double)((items + cus - 1) / cus) * (steps + 6.0) * w;

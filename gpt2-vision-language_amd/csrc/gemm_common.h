@@ -564,8 +564,8 @@ int gemm_pp3_launch_tf(const GemmP& p, const GemmSink& k);
 int gemm_pp3_launch_tt(const GemmP& p, const GemmSink& k);
 bool gemm_w4_plan(const GemmP& p, int a_mn, bool force);  // gemm_w4.hip
 int gemm_w4_launch(const GemmP& p, int b_mn, const GemmSink& k);  // (also the direct-A variant)
-bool gemm_w4d_ok(const GemmP& p, bool rows128);  // gemm_w4d_f.hip: direct-A variant for a w4-planned shape
-int gemm_w4d_launch(const GemmP& p, int b_mn, bool rows128, const GemmSink& k);
+bool gemm_w4d_ok(const GemmP& p);  // gemm_w4d_f.hip: direct-A variant for a w4-planned 192-row shape
+int gemm_w4d_launch(const GemmP& p, int b_mn, const GemmSink& k);
 bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force);  // gemm_w4x.hip: AGPR four-wave kernel
 bool w4x_dw_plan(GemmP& p);  // batched dW (a_mn, b_mn, C += AB): tile choice, false when not routed
 bool gemm_w4x_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& k);  // false: no instance

@@ -57,22 +57,12 @@ static int gemm_pp3_splits(int64_t M, int64_t N, int64_t K, int gran) {
 // Persistent-kernel plan: bf16 output with 16-B stores; tiles, split-K factor and K-slice
 // depth filled into p.  Without `force`, only when the work items fill the chip well enough
 // to beat the 128x128 ring (measured, tools/gemm_shapes.py): >= 160 items.
-// Work-item floor for the persistent kernel (GVL_PP3_MIN overrides it for A/B measurement).
-static int64_t pp3_min_items() {
-  static const int64_t v = [] {
-    const char* e = getenv("GVL_PP3_MIN");
-    const long x = e ? atol(e) : 0;
-    return (int64_t)(x > 0 ? x : 160);
-  }();
-  return v;
-}
+constexpr int64_t PP3_MIN_ITEMS = 160;  // work-item floor for the persistent kernel
 
 // Output tile width: 192 when its tiles fill the last round of CUs better than 256-wide ones
-// (per-tile efficiency of the narrower tile counted at 0.9); GVL_PP3_BN=256|192 forces one.
+// (per-tile efficiency of the narrower tile counted at 0.9).
 static int pp3_tile_width(int64_t M, int64_t N) {
-  static const int forced = env_int("GVL_PP3_BN", 0);
   if (N % 64 != 0 || N < 384) return 256;
-  if (forced == 256 || forced == 192) return forced;
   const int64_t cus = num_cus(), tm = (M + 255) / 256;
   auto fill = [&](int64_t tiles) {
     const int64_t rounds = (tiles + cus - 1) / cus;
@@ -114,23 +104,16 @@ static void pp3_choose_combined(GemmP& p, int gran) {
 
 // Tile height 128 (with 192-wide tiles) when its tiles fill the CUs in fewer rounds than the
 // 256-row tiles: estimated per-tile cost 0.375 / E128 of a 256x256 tile (E128 = per-FLOP
-// efficiency of the half-height tile, GVL_PP3_E128 x 100, default 70: measured equal to the
-// 128x128 ring at N = 768, 8 % slower than 256x192 at N = 2304); GVL_PP3_BM=128|256
-// forces the height (A/B).
+// efficiency of the half-height tile, 0.70: measured equal to the 128x128 ring at N = 768,
+// 8 % slower than 256x192 at N = 2304).
+constexpr double PP3_E128 = 0.70;
 static int pp3_tile_height(int64_t M, int64_t N, int bn) {
-  static const int forced = env_int("GVL_PP3_BM", 0);
-  static const double e128 = [] {
-    const char* e = getenv("GVL_PP3_E128");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v / 100.0 : 0.70;
-  }();
   if (N % 64 != 0 || N < 384) return 256;
-  if (forced == 256 || forced == 128) return forced;
   const int64_t cus = num_cus();
   auto rounds = [&](int64_t t) { return (double)((t + cus - 1) / cus); };
   const double w_bn = bn == 256 ? 1.0 : 0.75 / 0.9;
   const double t256 = rounds(((M + 255) / 256) * ((N + bn - 1) / bn)) * w_bn;
-  const double t128 = rounds(((M + 127) / 128) * ((N + 191) / 192)) * 0.375 / e128;
+  const double t128 = rounds(((M + 127) / 128) * ((N + 191) / 192)) * 0.375 / PP3_E128;
   return t128 < 0.95 * t256 ? 128 : 256;
 }
 
@@ -144,18 +127,13 @@ bool gemm_pp3_plan(GemmP& p, bool force, int gran) {
   int sp = 1;
   if (p.ws != nullptr) sp = gemm_pp3_splits(p.M, p.N, p.K, gran);
   // the persistent kernel's in-launch two-way combine for single GEMMs: measured slower than
-  // whole-K tiles, so only with GVL_PP3_COMBINE=1, whatever tickets the caller passes
-  // (since round 5 gvl.kernels always passes them, for the AGPR kernel's split, gemm_w4x.hip)
-  static const bool combine_env = [] {
-    const char* e = getenv("GVL_PP3_COMBINE");
-    return e && e[0] == '1';
-  }();
-  const bool combine_on = combine_env || pp3_combine_forced();  // (gvl_gemm_tune(3, 13): tests)
-  if (sp <= 2 && combine_on && p.ws != nullptr && p.tickets != nullptr && gemm_epi_kind(p) != EPI_GEN) {
+  // whole-K tiles, so only under gvl_gemm_tune(3, 13) (tests), whatever tickets the
+  // caller passes (gvl.kernels always passes them, for the AGPR kernel's split, gemm_w4x.hip)
+  if (sp <= 2 && pp3_combine_forced() && p.ws != nullptr && p.tickets != nullptr && gemm_epi_kind(p) != EPI_GEN) {
     p.bn = 256;
     pp3_choose_combined(p, gran);
     if (force) return true;
-    return (int64_t)p.tiles_m * p.tiles_n * p.splits >= pp3_min_items();
+    return (int64_t)p.tiles_m * p.tiles_n * p.splits >= PP3_MIN_ITEMS;
   }
   p.tickets = nullptr;  // slab split-K (gemm_splitk_reduce) or no split
   if (sp > 1 && (int64_t)sp * p.M * p.N * 4 <= p.ws_bytes) p.splits = sp;
@@ -174,7 +152,7 @@ bool gemm_pp3_plan(GemmP& p, bool force, int gran) {
   // split-K slabs only pay off for really few tiles (dW, the caption lm_head dX); with
   // >= 64 tiles the 128x128 ring at two workgroups per CU is faster
   if (p.splits > 1 && tiles >= 64) return false;
-  return tiles * p.splits >= pp3_min_items();
+  return tiles * p.splits >= PP3_MIN_ITEMS;
 }
 
 int gemm_pp3_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& k) {

@@ -411,11 +411,10 @@ int launch_pp3_bn(const GemmP& p0, const gvl::GemmSink& k) {
   hipStream_t s = k.stream;
   GemmP p = p0;  // tiles_m/n, splits, kper set by gemm_pp3_plan
   // counted epilogue (CntEpi): one problem, 32-bit store offsets below the dropped-store offset,
-  // a 16-B aligned bias row whose LDS copy fits after the ring (GVL_PP3_CNT=0: off, A/B)
-  static const bool cnt_env = gvl::env_on("GVL_PP3_CNT");
+  // a 16-B aligned bias row whose LDS copy fits after the ring
   constexpr int ring = NS * (BM + BN) * KS * 2;
   const int64_t bias_bytes = EpiKind<EPI>::BIAS ? 2 * (int64_t)p.tiles_n * BN : 0;
-  p.cnt = CntEpi<EPI>::ON && cnt_env && p.batch == 1 && ring + bias_bytes <= 160 * 1024 &&
+  p.cnt = CntEpi<EPI>::ON && p.batch == 1 && ring + bias_bytes <= 160 * 1024 &&
           p.M * p.ldc * 2 <= (int64_t)CNT_OOB &&
           (!EpiKind<EPI>::ACT || (p.pre_out != nullptr && p.M * p.ldp * 2 <= (int64_t)CNT_OOB)) &&
           (!EpiKind<EPI>::BIAS || ((reinterpret_cast<uintptr_t>(p.bias) & 15) == 0 && p.N % 8 == 0));
@@ -424,9 +423,8 @@ int launch_pp3_bn(const GemmP& p0, const gvl::GemmSink& k) {
   // alternated).  The caption step's 811 MB logits stay on the default policy: part of them is
   // still in the MALL when the CE kernel reads them (Q-Former step 15.21k vs 15.10k images/s
   // with nt); outputs that fit measured far slower (c_fc + GELU 64 -> 120 us in a loop that
-  // rewrites them).  profiles/r4/pp3_store_policy_r4n_r4s.txt; GVL_PP3_NT=0 off.
-  static const bool nt_env = gvl::env_on("GVL_PP3_NT");
-  p.st_nt = p.cnt && nt_env && p.M * p.ldc * 2 > (int64_t)1 << 30;
+  // rewrites them).  profiles/r4/pp3_store_policy_r4n_r4s.txt.
+  p.st_nt = p.cnt &&p.M * p.ldc * 2 > (int64_t)1 << 30;
   const int lds = ring + (p.cnt ? (int)bias_bytes : 0);
   auto kern = gemm_pp3_kernel<NS, AMN, BMN, EPI, BN, BM>;
   static bool attr_set = false;

@@ -367,25 +367,13 @@ namespace gvl {
 // Tile choice (measured, tools/gemm_sweep.sh on MI355X): the ping-pong 256x256 kernel once the
 // output has >= 192 of its tiles, except between 1 and 1.25 rounds of 256 CUs (a nearly empty
 // second round); else the 128x128 ring kernel at two workgroups per CU.
-// GVL_RING_SMALL=<cfg> (1 = 256x128, 6 = 64x128) overrides that choice for outputs of
-// 256..512 tiles of 128x128 (A/B measurement; tools/gpu_ab.sh).  64x128 measured on the
-// Q-Former caption step (its N = 768 GEMMs at M = 8064): dominant GEMM 0.198 -> 0.200 of
-// peak but the step 13.0k -> 12.8k img/s, so it is not the default.
-static int ring_band_cfg() {
-  static const int cfg = [] {
-    const char* e = getenv("GVL_RING_SMALL");
-    return (e && (e[0] == '1' || e[0] == '6') && e[1] == 0) ? e[0] - '0' : 2;
-  }();
-  return cfg;
-}
+// For outputs of 256..512 tiles of 128x128, 64x128 (config 6) was measured on the Q-Former
+// caption step (its N = 768 GEMMs at M = 8064): dominant GEMM 0.198 -> 0.200 of peak but the
+// step 13.0k -> 12.8k img/s, so 128x128 serves them too.
 int gemm_ring_pick(int64_t M, int64_t N, int64_t K, int forced, int a_mn) {
   if (forced >= 0) return forced;
   const int64_t t256 = ((M + 255) / 256) * ((N + 255) / 256);
-  if (t256 < 192 || (t256 > 256 && t256 <= 320)) {
-    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
-    if (!a_mn && t128 > 256 && t128 < 512) return ring_band_cfg();
-    return 2;
-  }
+  if (t256 < 192 || (t256 > 256 && t256 <= 320)) return 2;
   return 4;
 }
 }  // namespace gvl

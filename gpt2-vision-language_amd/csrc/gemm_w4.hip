@@ -46,36 +46,23 @@ GVL_DEV void w4_store(char* lds, const uint4* v, int wave, int lane) {
     *reinterpret_cast<uint4*>(lds + (t * NWV + wave) * 1024 + lane * 16) = v[t];
 }
 
-// 96-wide B slab of a 32-deep K-step (gemm_w4n_kernel: 128 x 96 tiles).
+// 96-row K-contiguous slab of a 32-deep K-step: the B slab of gemm_w4n_kernel (128 x 96 tiles,
+// the weight in forward GEMMs) and the A slab of gemm_w4r_kernel.
 // 6 KiB of operand in 1-KiB pieces over 4 waves: pieces j = 4t + wave, j < 6 real; waves 2-3's
 // second piece (j = 6, 7) is a dummy whose buffer offset is out of range (the load returns
 // zeros without touching memory) and whose LDS write lands in a 2 KiB pad no fragment reads,
-// so every wave runs the same branch-free staging code.
-//  * K-contiguous (the weight in forward GEMMs): [96 rows][32] 64-B rows, the Step image;
-//  * MN-contiguous (the weight in dX): cols 0-63 as [32][64] 128-B rows (Step192's tail image,
-//    f2 swizzle), cols 64-95 as [32][32] 64-B rows at +4 KiB, chunk c of k-row kr at
-//    c ^ f3(kr): the ds_read_b64_tr_b16 lane groups of the fragment pattern below hit 32
-//    distinct 8-B bank pairs (checked exhaustively, like attn_swizzle_check.py).
+// so every wave runs the same branch-free staging code.  Image: [96 rows][32] 64-B rows, as
+// Step's.  (An MN-contiguous 96-column image for the dX weight was measured slower than the
+// 128-column one and is gone: DESIGN, settled variants.)
 constexpr uint32_t W4_OOB = 0x7FFFFFF0u;
-GVL_DEV int f3(int k) { return (k >> 2) & 2; }  // 64-B rows
-template <bool MN, int NWV = 4>
 struct Step96 {
-  static constexpr int R = 96;
   static constexpr int REAL = 6;
   static constexpr int BYTES = 8 * 1024;  // 6 KiB image + 2 KiB pad for the dummy pieces
   static constexpr int PER = 2;
-  static_assert(NWV == 4, "four waves");
+  static constexpr int NWV = 4;
   GVL_DEV static int64_t elem(int64_t ld, int64_t r0, int64_t k0, int j, int lane) {
-    if (!MN) {
-      const int row = 16 * j + (lane >> 2);
-      return (r0 + row) * ld + k0 + ((lane & 3) ^ f64b(row)) * 8;
-    }
-    if (j < 4) {
-      const int kr = 8 * j + (lane >> 3);
-      return (k0 + kr) * ld + r0 + ((lane & 7) ^ f2(kr)) * 8;
-    }
-    const int kr = 16 * (j - 4) + (lane >> 2);
-    return (k0 + kr) * ld + r0 + 64 + ((lane & 3) ^ f3(kr)) * 8;
+    const int row = 16 * j + (lane >> 2);
+    return (r0 + row) * ld + k0 + ((lane & 3) ^ f64b(row)) * 8;
   }
   GVL_DEV static void base_offsets(int64_t ld, int64_t r0, int64_t k0, int wave, int lane,
                                    int (&off)[PER]) {
@@ -85,36 +72,19 @@ struct Step96 {
       off[t] = j < REAL ? (int)(elem(ld, r0, k0, j, lane) * 2) : (int)W4_OOB;
     }
   }
-  GVL_DEV static int step_bytes(int64_t ld) { return MN ? (int)(KS * ld * 2) : KS * 2; }
+  GVL_DEV static int step_bytes(int64_t) { return KS * 2; }
   GVL_DEV static short8_t frag(const char* lds, int c0, int lane) {
-    if (!MN) {
-      const int row = c0 + (lane & 15), ch = lane >> 4;
-      return *reinterpret_cast<const short8_t*>(lds + row * 64 + ((ch ^ f64b(row)) << 4));
-    }
-    const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int kr = 8 * G + q;
-    short8_t r;
-    if (c0 < 64) {
-      const int ch = (c0 >> 3) + (p >> 1);
-      const int off1 = kr * 128 + ((ch ^ f2(kr)) << 4) + (p & 1) * 8;
-      r.lo = lds_read_tr(lds + off1);
-      r.hi = lds_read_tr(lds + off1 + 4 * 128);
-    } else {
-      const int ch = ((c0 - 64) >> 3) + (p >> 1);
-      const int off1 = kr * 64 + ((ch ^ f3(kr)) << 4) + (p & 1) * 8;
-      r.lo = lds_read_tr(lds + 4096 + off1);
-      r.hi = lds_read_tr(lds + 4096 + off1 + 4 * 64);
-    }
-    return r;
+    const int row = c0 + (lane & 15), ch = lane >> 4;
+    return *reinterpret_cast<const short8_t*>(lds + row * 64 + ((ch ^ f64b(row)) << 4));
   }
 };
 template <int BN, bool MN>
 struct W4SlabB {
   using type = Step<BN, MN, 4>;
 };
-template <bool MN>
-struct W4SlabB<96, MN> {
-  using type = Step96<MN>;
+template <>
+struct W4SlabB<96, false> {  // (K-contiguous B only: launch_w4)
+  using type = Step96;
 };
 // A slab (K-contiguous): the Step image, or Step96's [96 rows][32] one for 96-row tiles
 template <int BM>
@@ -123,7 +93,7 @@ struct W4SlabA {
 };
 template <>
 struct W4SlabA<96> {
-  using type = Step96<false>;
+  using type = Step96;
 };
 
 // K-steps are 32 deep; the register staging runs P = 3 steps ahead of the LDS writes, the LDS
@@ -316,14 +286,6 @@ __global__ __launch_bounds__(256, 1) void gemm_w4r_kernel(GemmP p) {
 
 constexpr int W4_NS = 3;  // LDS ring slots (gemm_w4_body's ring geometry)
 
-// Tile walk: XCD-contiguous work items, then groups of `group` tile rows walked row-fastest.
-// GVL_W4_GROUP=1 walks all column tiles of a row block before the next one, so an XCD reads
-// each A row block once (and every column block of B); default: the GEMM-wide group.
-int w4_group(int dflt) {
-  static const int g = gvl::env_int("GVL_W4_GROUP", 0);
-  return g > 0 ? g : dflt;
-}
-
 // the kernel of a tile shape (if constexpr: only the chosen one is instantiated)
 template <int BM, int BN, bool BMN, int EPI>
 constexpr auto w4_kernel_of() {
@@ -346,7 +308,6 @@ int launch_w4_bm(const GemmP& p0, const gvl::GemmSink& k) {
   p.tiles_n = (int)((p.N + BN - 1) / BN);
   p.splits = 1;
   p.kper = p.K;
-  p.group = w4_group(p.group);
   constexpr int slot = W4SlabA<BM>::type::BYTES + W4SlabB<BN, BMN>::type::BYTES;
   constexpr int lds = NS * slot;
   auto kern = w4_kernel_of<BM, BN, BMN, EPI>();
@@ -362,12 +323,10 @@ int launch_w4_bm(const GemmP& p0, const gvl::GemmSink& k) {
 }
 
 // 128-row tiles where 192-row ones fill under 3/4 of the CUs and 128-row ones fill more
-// (GVL_W4_BM128=0: always 192, A/B)
 bool w4_use128(const GemmP& p) {
-  static const bool on = gvl::env_on("GVL_W4_BM128");
   const int64_t cus = gvl::num_cus(), tn = (p.N + W4_BN - 1) / W4_BN;
   const int64_t t192 = (p.M + 191) / 192 * tn, t128 = (p.M + 127) / 128 * tn;
-  return on && t192 * 4 < cus * 3 && t128 > t192 && t128 <= cus;
+  return t192 * 4 < cus * 3 && t128 > t192 && t128 <= cus;
 }
 
 // 128 x 96 tiles (gemm_w4n_kernel) where 128-row tiles are used and 96-column ones fill more
@@ -378,11 +337,9 @@ bool w4_use128(const GemmP& p) {
 // (profiles/r6/w4n_bn96_r6c.txt, 3968 / 4096 rows): the forward products (K-contiguous weight)
 // gain 8-10 % (attn.c_proj + bias + residual 16.3 -> 14.5 us, mlp.c_proj 39.1 -> 35.3), the dX
 // ones (MN-contiguous weight, whose 32-column image is fetched as 64-B row segments) lose 6-8 %
-// (c_fc.dX 35.8 -> 38.5), so only K-contiguous B takes them (GVL_W4_BN96=2: both, A/B).
-// GVL_W4_BN96=0: 128 x 128 as before (A/B).
-bool w4_use96(const GemmP& p, bool b_mn) {
-  static const int mode = gvl::env_int("GVL_W4_BN96", 1);
-  if (mode == 0 || (b_mn && mode < 2) || !w4_use128(p)) return false;
+// (c_fc.dX 35.8 -> 38.5), so only K-contiguous B takes them (launch_w4).
+bool w4_use96(const GemmP& p) {
+  if (!w4_use128(p)) return false;
   const int64_t cus = gvl::num_cus(), tm = (p.M + 127) / 128;
   const int64_t t128 = tm * ((p.N + 127) / 128), t96 = tm * ((p.N + 95) / 96);
   return t96 > t128 && t96 <= cus;
@@ -392,10 +349,9 @@ bool w4_use96(const GemmP& p, bool b_mn) {
 // where 128-row tiles are used and 96-row ones fill more of the chip in one round: the cross-att
 // decoder's 3968 text rows, 186 -> 252 tiles at N = 768.  The 128-column B image keeps its full
 // 256-B rows (the 96-column one of gemm_w4n_kernel lost on dX: 64-B row segments); the A slab is
-// Step96's [96][32] image (two dummy pieces).  GVL_W4_BM96=0: off (A/B).
-bool w4_use96r(const GemmP& p, bool b_mn) {
-  static const bool on = gvl::env_on("GVL_W4_BM96");
-  if (!on || !b_mn || !w4_use128(p)) return false;
+// Step96's [96][32] image (two dummy pieces).
+bool w4_use96r(const GemmP& p) {
+  if (!w4_use128(p)) return false;
   const int64_t cus = gvl::num_cus(), tn = (p.N + 127) / 128;
   const int64_t t128 = (p.M + 127) / 128 * tn, t96 = (p.M + 95) / 96 * tn;
   return t96 > t128 && t96 <= cus;
@@ -404,9 +360,11 @@ bool w4_use96r(const GemmP& p, bool b_mn) {
 template <bool BMN, int EPI>
 int launch_w4(const GemmP& p, const gvl::GemmSink& s) {
   if constexpr (BMN && EPI == EPI_PLAIN) {
-    if (w4_use96r(p, BMN)) return launch_w4_bm<BMN, EPI, 96, 128>(p, s);
+    if (w4_use96r(p)) return launch_w4_bm<BMN, EPI, 96, 128>(p, s);
   }
-  if (w4_use96(p, BMN)) return launch_w4_bm<BMN, EPI, 128, 96>(p, s);
+  if constexpr (!BMN) {
+    if (w4_use96(p)) return launch_w4_bm<BMN, EPI, 128, 96>(p, s);
+  }
   return w4_use128(p) ? launch_w4_bm<BMN, EPI, 128>(p, s) : launch_w4_bm<BMN, EPI, 192>(p, s);
 }
 
@@ -416,8 +374,7 @@ int launch_w4(const GemmP& p, const gvl::GemmSink& s) {
 // gated xattn.c_proj GEMMs per step (3968 x 768 x 768) fell to the 128 x 128 ring kernel's
 // runtime-flag epilogue for that reason: 32 us each, 0.058 of peak.
 int w4_epi_kind(const GemmP& p) {
-  static const bool gate_on = gvl::env_on("GVL_W4_GATE");  // =0: the generic path as before (A/B)
-  if (gate_on && p.gate && p.bias && p.residual && p.pre_out && !p.has_drop && !p.c_f32 && !p.act &&
+  if (p.gate && p.bias && p.residual && p.pre_out && !p.has_drop && !p.c_f32 && !p.act &&
       !p.dact)
     return EPI_GATE_RES;
   return gvl::gemm_epi_kind(p);
@@ -443,12 +400,6 @@ int launch_w4_epi(const GemmP& p, const gvl::GemmSink& s) {
   }
 }
 
-// Routing: GVL_W4=0 disables, =2 forces it for every shape it supports (tests / A/B).
-int w4_mode() {
-  static const int v = gvl::env_int("GVL_W4", 1);
-  return v;
-}
-
 }  // namespace
 
 namespace gvl {
@@ -459,17 +410,14 @@ bool gemm_w4_plan(const GemmP& p, int a_mn, bool force) {
   if (a_mn || p.c_f32 || p.K % (6 * KS) != 0 || p.N % 8 != 0 || p.ldc % 8 != 0) return false;
   if (p.pre_out && (p.ldp % 8 != 0 || (reinterpret_cast<uintptr_t>(p.pre_out) & 15))) return false;
   if (w4_epi_kind(p) == EPI_GEN || w4_epi_kind(p) == EPI_BIAS_QGELU) return false;
-  if (force || w4_mode() == 2) return true;
-  if (w4_mode() == 0) return false;
-  // GVL_W4=3 (A/B): also the short-K wide outputs (K <= 1024, N <= 4096: c_attn / c_fc
-  // forward, mlp.c_proj dX), whose 192x256 ping-pong tiles run only 24 K-steps each —
-  // measured slower (profiles/r2/r2i/w4s_shapes.txt: 575 vs 790 TF/s at M = 16384).
-  if (w4_mode() == 3 && p.K <= 1024 && p.N <= 4096) return true;
+  if (force) return true;
+  // (not the short-K wide outputs, K <= 1024, N <= 4096: c_attn / c_fc forward, mlp.c_proj dX,
+  // whose 192x256 ping-pong tiles run only 24 K-steps each — measured slower here,
+  // profiles/r2/r2i/w4s_shapes.txt: 575 vs 790 TF/s at M = 16384)
   const int64_t cus = num_cus();
   const int64_t t256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
   const int64_t tw4 = ((p.M + W4_BM - 1) / W4_BM) * ((p.N + W4_BN - 1) / W4_BN);
   if (p.N > 1024 || t256 >= 160 || tw4 > cus) return false;
-  if (w4_mode() == 4) return tw4 * 2 >= cus;  // GVL_W4=4: the round-2 half-chip rule (A/B)
   if (tw4 * 4 >= cus * 3) return true;
   // 40-75 % of the CUs (the cross-att decoder's 3968 text rows: 126 tiles) only with a K short
   // enough that one tile per CU beats splitting K (the caption lm_head dX, K = 50304, and the
@@ -478,13 +426,13 @@ bool gemm_w4_plan(const GemmP& p, int a_mn, bool force) {
 }
 
 int gemm_w4_launch(const GemmP& p, int b_mn, const GemmSink& s) {
-  if (gemm_w4d_ok(p, w4_use128(p))) {
+  if (!w4_use128(p) && gemm_w4d_ok(p)) {
     // direct-A tiles walk all column tiles of a row block before the next one, so an XCD reads
     // each A row block once: HBM bytes per Q-Former dX launch 104 -> 80 MB at equal time
-    // (profiles/r3/w4d_group_ab_r3s2.txt); GVL_W4_GROUP overrides
+    // (profiles/r3/w4d_group_ab_r3s2.txt)
     GemmP q = p;
-    q.group = w4_group(1);
-    return gemm_w4d_launch(q, b_mn, w4_use128(q), s);
+    q.group = 1;
+    return gemm_w4d_launch(q, b_mn, s);
   }
   return b_mn ? launch_w4_epi<true>(p, s) : launch_w4_epi<false>(p, s);
 }

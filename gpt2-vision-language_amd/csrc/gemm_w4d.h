@@ -305,31 +305,21 @@ template <bool BMN, int EPI>
 __global__ __launch_bounds__(256, 1) void gemm_w4d_kernel(GemmP p) {
   gemm_w4d_body<BMN, EPI, 192>(p);
 }
-template <bool BMN, int EPI>
-__global__ __launch_bounds__(256, 1) void gemm_w4dm_kernel(GemmP p) {
-  gemm_w4d_body<BMN, EPI, 128>(p);
-}
 
-template <bool BMN, int EPI, int BM>
-int launch_bm(const GemmP& p0, const gvl::GemmSink& k) {
-  if (gvl::gemm_name_only(k, "%s<%s, %d>", BM == 192 ? "gemm_w4d_kernel" : "gemm_w4dm_kernel", gvl::tf(BMN), EPI))
-    return 0;
+template <bool BMN, int EPI>
+int launch_w4d(const GemmP& p0, const gvl::GemmSink& k) {
+  if (gvl::gemm_name_only(k, "gemm_w4d_kernel<%s, %d>", gvl::tf(BMN), EPI)) return 0;
   GemmP p = p0;
-  p.tiles_m = (int)((p.M + BM - 1) / BM);
+  p.tiles_m = (int)((p.M + 191) / 192);
   p.tiles_n = (int)((p.N + D_BN - 1) / D_BN);
   p.splits = 1;
   p.kper = p.K;
   constexpr int lds = 3 * D_SLOT;
-  auto kern = BM == 192 ? gemm_w4d_kernel<BMN, EPI> : gemm_w4dm_kernel<BMN, EPI>;
+  auto kern = gemm_w4d_kernel<BMN, EPI>;
   const int total = p.tiles_m * p.tiles_n;
   const int grid = total < gvl::num_cus() ? total : gvl::num_cus();
   gvl::launch_timed(kern, dim3(grid), dim3(256), lds, k.stream, p);
   return 0;
-}
-
-template <bool BMN, int EPI>
-int launch_rows(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
-  return rows128 ? launch_bm<BMN, EPI, 128>(p, s) : launch_bm<BMN, EPI, 192>(p, s);
 }
 
 // the epilogues the caption decoders and the Q-Former route to the four-wave kernels
@@ -338,13 +328,13 @@ inline bool epi_supported(int e) {
 }
 
 template <bool BMN>
-int launch_epi(const GemmP& p, bool rows128, const gvl::GemmSink& s) {
+int launch_epi(const GemmP& p, const gvl::GemmSink& s) {
   switch (gvl::gemm_epi_kind(p)) {
-    case EPI_PLAIN: return launch_rows<BMN, EPI_PLAIN>(p, rows128, s);
-    case EPI_BIAS_RES: return launch_rows<BMN, EPI_BIAS_RES>(p, rows128, s);
-    case EPI_BIAS: return launch_rows<BMN, EPI_BIAS>(p, rows128, s);
-    case EPI_RES: return launch_rows<BMN, EPI_RES>(p, rows128, s);
-    case EPI_BIAS_DROP_RES: return launch_rows<BMN, EPI_BIAS_DROP_RES>(p, rows128, s);
+    case EPI_PLAIN: return launch_w4d<BMN, EPI_PLAIN>(p, s);
+    case EPI_BIAS_RES: return launch_w4d<BMN, EPI_BIAS_RES>(p, s);
+    case EPI_BIAS: return launch_w4d<BMN, EPI_BIAS>(p, s);
+    case EPI_RES: return launch_w4d<BMN, EPI_RES>(p, s);
+    case EPI_BIAS_DROP_RES: return launch_w4d<BMN, EPI_BIAS_DROP_RES>(p, s);
     default: return -1;
   }
 }

@@ -2,7 +2,7 @@
 #include "gemm_w4d.h"
 
 namespace gvl {
-int gemm_w4d_launch_t(const GemmP& p, bool rows128, const GemmSink& s) {
-  return launch_epi<true>(p, rows128, s);
+int gemm_w4d_launch_t(const GemmP& p, const GemmSink& s) {
+  return launch_epi<true>(p, s);
 }
 }  // namespace gvl

@@ -417,32 +417,19 @@ __global__ __launch_bounds__(256, 1) void gemm_w4x_kernel(GemmP p) {
   gemm_w4x_body<BM, BN, AMN, BMN, EPI, GR>(p);
 }
 
-// Weight-gradient launches (AMN && BMN: the LM's batched / grouped dW over 16384 tokens, 3-7
-// rounds of whole-K tiles) and their grid (the grouped launch reads 2.16x its
-// operand bytes).  The three 256-column tiles that share a dY slab sit next to each other in an
-// XCD's work range, but in a persistent grid (one workgroup per CU walking vid += G) each starts
-// when ITS CU finished its previous tile, so after a few rounds the siblings are far apart and
-// the slab is fetched again by the late one.  GVL_W4X_NP=1: one workgroup per tile instead
-// (grid = tiles); the XCD's dispatcher hands the next tile of its contiguous range to the first
-// CU that frees up, so siblings start within one tile-retire of each other in every round.
-// GVL_W4X_DW_GROUP=n: tile rows per L2 group of the dW tile walk (default: the GEMM's).
-int w4x_np_mode() {
-  static const int v = gvl::env_int("GVL_W4X_NP", 0);
-  return v;
-}
-int w4x_dw_group(int dflt) {
-  static const int v = gvl::env_int("GVL_W4X_DW_GROUP", 0);
-  return v > 0 ? v : dflt;
-}
-
+// Persistent grid: one workgroup per CU walking vid += G, for the weight-gradient launches
+// (AMN && BMN: the LM's batched / grouped dW over 16384 tokens, 3-7 rounds of whole-K tiles)
+// too.  Their grouped launch reads 2.16x its operand bytes: the three
+// 256-column tiles that share a dY slab sit next to each other in an XCD's work range, but each
+// starts when ITS CU finished its previous tile, so after a few rounds the siblings are far
+// apart and the slab is fetched again by the late one.  One workgroup per tile (grid = tiles)
+// was measured against that: 9 % less traffic, time and LM step unchanged (DESIGN, settled
+// variants).
 template <int BM, int BN, bool AMN, bool BMN, int EPI, bool GR = false>
-void launch_w4x(const GemmP& p0, const gvl::GemmSink& k) {
+void launch_w4x(const GemmP& p, const gvl::GemmSink& k) {
   if (gvl::gemm_name_only(k, "gemm_w4x_kernel<%d, %d, %s, %s, %d, %s>", BM, BN, gvl::tf(AMN), gvl::tf(BMN), EPI,
                           gvl::tf(GR)))
     return;
-  GemmP p = p0;
-  constexpr bool DW = AMN && BMN;
-  if constexpr (DW) p.group = w4x_dw_group(p.group);
   auto kern = gemm_w4x_kernel<BM, BN, AMN, BMN, EPI, GR>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -450,8 +437,7 @@ void launch_w4x(const GemmP& p0, const gvl::GemmSink& k) {
     attr_set = true;
   }
   const int total = GR ? p.gtile[p.batch] : p.tiles_m * p.tiles_n * p.batch;
-  const bool np = DW ? w4x_np_mode() >= 1 : w4x_np_mode() >= 2;
-  const int grid = (np || total < gvl::num_cus()) ? total : gvl::num_cus();
+  const int grid = total < gvl::num_cus() ? total : gvl::num_cus();
   constexpr int lds = x_ns<BM>() * (BM + BN) * KS * 2;
   gvl::launch_timed(kern, dim3(grid), dim3(256), lds, k.stream, p);
 }
@@ -468,17 +454,11 @@ bool launch_w4x_epi(const GemmP& p, const gvl::GemmSink& s) {
 
 namespace gvl {
 
-// GVL_W4X: 0 never, 1 the shapes below (default), 2 every shape the kernel takes (tests);
-// gvl_gemm_tune(3, 12) forces it too.  LM step 885k -> 900k tokens/s, same box, alternated
-// (profiles/r4/w4x_lm_ab_r4p.txt)
-int w4x_mode() {
-  static const int m = env_int("GVL_W4X", 1);
-  return m;
-}
-
 // The kernel takes K-contiguous A (activations / dY), either B layout, bf16 out, K % 32 == 0,
 // plain or bias + residual epilogues, one problem, no split.  Routed: outputs whose 256 x 192
-// tiling fills the chip in whole rounds (M = 16384, N = 768: 256 tiles).
+// tiling fills the chip in whole rounds (M = 16384, N = 768: 256 tiles); gvl_gemm_tune(3, 12)
+// forces it for every shape it takes.  LM step 885k -> 900k tokens/s, same box, alternated
+// (profiles/r4/w4x_lm_ab_r4p.txt)
 bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force) {
   const int epi = gemm_epi_kind(p);
   if (a_mn) return p.batch == 1 && w4x_dw_plan(p) && p.K >= 4096;  // the lm_head's dW (b_mn)
@@ -495,21 +475,18 @@ bool gemm_w4x_plan(GemmP& p, int a_mn, int b_mn, bool force) {
   p.tiles_n = (int)tn;
   p.splits = 1;
   p.kper = p.K;
-  if (force || w4x_mode() == 2) return true;
-  if (w4x_mode() == 0) return false;
+  if (force) return true;
   const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
   if (p.bm == 256) return p.N == 768 && tiles >= cus && tiles % cus == 0;
-  // 128-row tiles (GVL_W4X_128: 0 never, 1 wherever they fill one round, 2 = default: only where
-  // the direct-A kernel's 192 x 128 tiles overflow one round).  At the Q-Former / cross decoders'
+  // 128-row tiles only where the direct-A kernel's 192 x 128 tiles overflow one round (not
+  // wherever they fill one round).  At the Q-Former / cross decoders'
   // 8064 rows the direct-A kernel fills one round (252 tiles) and is faster in the step (round 4
   // r4r and round 5 r5a: 15.45k vs 15.63k images/s with 128-row AGPR tiles); the linear caption
   // decoder's 8192 rows are 258 of its tiles (a second round for 2 tiles), which sent those
   // GEMMs to the 128 x 128 ring kernel (59-71 us, 30 % of the linear step in r5g) — here they
   // are exactly 256 tiles of 128 x 192
-  static const int rows128 = env_int("GVL_W4X_128", 2);
   const int64_t t_direct = ((p.M + 191) / 192) * ((p.N + 127) / 128);
-  const bool want = rows128 == 1 || (rows128 == 2 && t_direct > cus);
-  return want && p.N == 768 && tiles * 10 >= cus * 9 && tiles <= cus;
+  return t_direct > cus && p.N == 768 && tiles * 10 >= cus * 9 && tiles <= cus;
 }
 
 // p planned by gemm_w4x_plan (one problem) or w4x_dw_plan (a batch of weight gradients).
@@ -534,10 +511,7 @@ bool gemm_w4x_launch(const GemmP& p, int a_mn, int b_mn, const GemmSink& s) {
 // the persistent kernel; 12 c_fc / mlp.c_proj ones as 576 such tiles, a third round 25 % full:
 // 1109 / 1014 vs 989 / 964, profiles/r4/w4x_r4r.txt — 256 x 256 gives them 432).  The 12
 // attn.c_proj problems (144 / 108 tiles) keep the persistent kernel's in-launch K split.
-// GVL_W4X_DW=0 turns it off (A/B).
 bool w4x_dw_plan(GemmP& p) {
-  static const bool on = env_on("GVL_W4X_DW");
-  if (!on || w4x_mode() == 0) return false;
   if (gemm_epi_kind(p) != EPI_RES || p.c_f32 || p.K % KS != 0 || p.K < 2 * KS || p.M % 8 != 0 ||
       p.N % 8 != 0 || p.ldc % 8 != 0 || p.lda % 8 != 0 || p.ldb % 8 != 0)
     return false;
@@ -560,10 +534,9 @@ bool w4x_dw_plan(GemmP& p) {
 // bias sums fused): whole-K 256 x 256 tiles, the problems' tile lists concatenated (GemmP::gtile);
 // each problem alone would be 9-36 tiles and a split-K launch + reduce + a column-sum pair.
 // Tiles of 256 x 256 or 256 x 192, whichever fills the last round better.
-// p: batch, Ab / Bb / Cb / Db and the per-problem sizes set by the caller.  GVL_W4X_GR=0 off.
+// p: batch, Ab / Bb / Cb / Db and the per-problem sizes set by the caller.
 bool gemm_w4x_grouped_try(GemmP& p, const GemmSink& s) {
-  static const bool on = env_on("GVL_W4X_GR");
-  if (!on || w4x_mode() == 0 || p.batch < 1 || p.batch > GVL_MAX_GROUP) return false;
+  if (p.batch < 1 || p.batch > GVL_MAX_GROUP) return false;
   int64_t t192 = 0, t256 = 0;
   for (int i = 0; i < p.batch; ++i) {
     if (p.Kb[i] % KS != 0 || p.Kb[i] < 2 * KS || p.Mb[i] % 8 != 0 || p.Nb[i] % 8 != 0 ||
@@ -576,10 +549,6 @@ bool gemm_w4x_grouped_try(GemmP& p, const GemmSink& s) {
   const int64_t cus = num_cus();
   auto fill = [&](int64_t tiles) { return (double)tiles / (double)(((tiles + cus - 1) / cus) * cus); };
   p.bn = fill(t256) >= 0.95 * fill(t192) ? 256 : 192;
-  // GVL_W4X_GR_BN=192|256 forces the tile width (A/B; read per call)
-  if (const char* e = getenv("GVL_W4X_GR_BN")) {
-    if (atoi(e) == 192 || atoi(e) == 256) p.bn = atoi(e);
-  }
   int t = 0;
   for (int i = 0; i < p.batch; ++i) {
     p.gtile[i] = t;

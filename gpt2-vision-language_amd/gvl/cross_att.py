@@ -6,7 +6,6 @@ frozen at (1, 0).  Compute: CrossAttnFn + GPTBlockFn per block on the HIP path.
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 
 import torch
@@ -17,10 +16,6 @@ from .functional import bf
 from .gpt2 import MLP, build_optimizer, init_gpt_weights
 from .gpt2 import CausalSelfAttention as CausalSelfAttention  # with the mask buffer (:19)
 from .caption import pool_clip_197_to_33_avg_with_cls
-
-# kv_proj of all blocks as one GEMM over the shared z_proj (Fn.CrossKVFn); GVL_XKV_BATCH=0 runs
-# each block's own kv_proj inside Fn.CrossAttnFn (A/B).
-XKV_BATCH = os.environ.get("GVL_XKV_BATCH", "1") != "0"
 
 __all__ = ["GPTConfig", "CausalSelfAttention", "CrossAttention", "MLP", "Vision_projector",
            "Block", "GPT", "pool_clip_197_to_33_avg_with_cls"]
@@ -175,7 +170,7 @@ class GPT(nn.Module):
         zp = kv = None
         if z is not None:
             zp = tr.vis_proj(z).to(dtype=x.dtype)
-            if XKV_BATCH and len(tr.h) > 1:
+            if len(tr.h) > 1:  # kv_proj of all blocks as one GEMM over the shared zp
                 slab = Fn.KVGradSlab(len(tr.h))
                 wb = [bf(t) for blk in tr.h for t in (blk.xattn.kv_proj.weight, blk.xattn.kv_proj.bias)]
                 kv = Fn.CrossKVFn.apply(zp, slab, *wb)

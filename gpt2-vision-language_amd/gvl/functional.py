@@ -107,9 +107,8 @@ def pad_vocab(w):
 # both uses into its one arena gradient (LMHeadLossFn's GEMM epilogue, EmbedFn's row update).
 FUSE_GRAD_ACC = True
 # MLP GELU: the forward epilogue stores gelu'(x) instead of x (GEMM act 3/4) and the backward
-# multiplies by it (dact 3), so the dX epilogue runs no transcendentals.  0 (GVL_GELU_DERIV=0)
-# stores x and recomputes gelu'(x) in the dX epilogue (act 1/2, dact 1/2).
-GELU_DERIV = 0 if os.environ.get("GVL_GELU_DERIV", "1") == "0" else 2
+# multiplies by it (dact 3), so the dX epilogue runs no transcendentals
+# (profiles/r2/ab_gelu_deriv_r2e.txt).
 _READY_HOOKS = []
 # Deferred weight gradients: a sunk nn.Linear weight gradient (dY^T X added into .grad) and
 # bias gradient (column sums of dY) are queued instead of launched, and at the end of the backward pass (an autograd engine final
@@ -120,29 +119,22 @@ _READY_HOOKS = []
 # bias column sums (96 small launches) become 4 launch pairs (gvl_colsum_batched).
 # The per-block units repeated 12 times defer (GPTBlockFn, CrossAttnFn) and are flushed as
 # batched launches per shape.  The bridge units (MLPFn, MHAFn's out_proj, LinearFn) defer too
-# (GVL_DEFER_BRIDGE, round 4): their few problems of different shapes are flushed as ONE grouped
+# (round 4): their few problems of different shapes are flushed as ONE grouped
 # launch (gvl_gemm_grouped) with the bias sums fused, instead of one split-K launch + reduce +
 # column-sum pair each (round 2 measured plain deferral of the bridge 0.5 % slower: per-shape
-# batches of 2 problems underfill the chip).  GVL_DEFER_WGRAD=0 launches each one in place.
-DEFER_WGRAD = os.environ.get("GVL_DEFER_WGRAD", "1") != "0"
-DEFER_BRIDGE = os.environ.get("GVL_DEFER_BRIDGE", "1") != "0"
-DEFER_INPROJ = os.environ.get("GVL_DEFER_INPROJ", "1") != "0"  # MHAFn's packed in_proj slices too
+# batches of 2 problems underfill the chip); MHAFn's packed in_proj row slices go with them.
 # The tied lm_head's weight gradient (dlogits^T x, scaled by the device scalar dloss / count) is
-# queued too (round 5), so the LM flush can group it with the blocks' (_flush_grouped)
-DEFER_LMHEAD = os.environ.get("GVL_DEFER_LMHEAD", "1") != "0"
+# queued too (round 5), so the LM flush can group it with the blocks' (_flush_grouped).
 # LayerNorm weight / bias gradients (round 5, ABI v12): the backward leaves its per-block column
 # partials in a workspace and the flush reduces all of them in one launch
-# (gvl_layernorm_bwd_finalize_batched) instead of one finalize launch per LayerNorm
-DEFER_LN = os.environ.get("GVL_DEFER_LN", "1") != "0"
-# The cross-att tanh gate's gradient added into its bf16 grad by the gate kernel itself (ABI v13)
-# instead of an fp32 zero-fill + kernel + cast + autograd add per block (GVL_GATE_SINK=0: A/B)
-GATE_SINK = os.environ.get("GVL_GATE_SINK", "1") != "0"
+# (gvl_layernorm_bwd_finalize_batched) instead of one finalize launch per LayerNorm.
+# The cross-att tanh gate's gradient is added into its bf16 grad by the gate kernel itself
+# (ABI v13) instead of an fp32 zero-fill + kernel + cast + autograd add per block.
 # Grouped flush (gvl_gemm_grouped) of the queued weight gradients of one stream over <= 8192
-# tokens: 2 (default) up to 48 problems (the cross-att decoder's 12 blocks' flush: +1.9 % on its
-# step, profiles/r4/grouped48_r4g48.txt), 1 up to 16 (the Q-Former bridge's), 0 off.  The LM's
-# K = 16384 flushes stay per-shape batches: all 48 of them as one grouped launch measured 3070
-# vs 2942 us and the LM step 924k vs 933.6k tokens/s (same box).
-GROUPED_WGRAD = int(os.environ.get("GVL_GROUPED_WGRAD", "2"))
+# tokens: up to GROUPED_MAX problems (the cross-att decoder's 12 blocks' flush: +1.9 % on its
+# step against 16, profiles/r4/grouped48_r4g48.txt).  The LM's K = 16384 flushes stay per-shape
+# batches except for the shapes _flush_grouped picks: all 48 of them as one grouped launch
+# measured 3070 vs 2942 us and the LM step 924k vs 933.6k tokens/s (same box).
 GROUPED_MAX = 48
 # Queue entries are tagged with the autograd graph task that produced them, and every task
 # that defers queues its OWN end-of-backward flush, which runs only that task's entries: two
@@ -256,7 +248,7 @@ def flush_wgrads(task=None):
         key = (tuple(dy2.shape), dy2.stride(0), tuple(x2.shape), x2.stride(0), g.stride(0),
                dy2.device, ap, st)
         groups.setdefault(key, []).append((p, g, dy2, x2))
-    if GROUPED_WGRAD and len(groups) >= 2:
+    if len(groups) >= 2:
         groups = _flush_grouped(groups, paired, _done)
     order = list(groups.items())
     ready = []
@@ -319,9 +311,8 @@ def _tiles256(its):
 def _flush_grouped(groups, paired, done):
     """Queued weight gradients of one stream as one grouped launch (gvl_gemm_grouped); returns
     the groups left to the per-shape path.
-    * Flushes over <= 8192 tokens (the caption steps): all of them, at most GROUPED_MAX
-      (GROUPED_WGRAD 1: 16).
-    * Larger ones (the LM's 16k-token micro-step, GROUPED_WGRAD 2): the shapes of >= 16 tiles per
+    * Flushes over <= 8192 tokens (the caption steps): all of them, at most GROUPED_MAX.
+    * Larger ones (the LM's 16k-token micro-step): the shapes of >= 16 tiles per
       problem (c_attn, c_fc, mlp.c_proj and the tied lm_head's dW, scaled by its device scalar),
       when one launch over all their tiles takes fewer whole rounds of CUs than the per-shape
       launches (each a whole number of rounds; under one round they split K), counting the
@@ -331,12 +322,10 @@ def _flush_grouped(groups, paired, done):
         return groups
     items = [it for its in groups.values() for it in its]
     if all(it[2].shape[0] <= 8192 for it in items):
-        if len(items) > (GROUPED_MAX if GROUPED_WGRAD >= 2 else 16):
+        if len(items) > GROUPED_MAX:
             return groups
         sel = groups
     else:
-        if GROUPED_WGRAD < 2:
-            return groups
         sel = {k: its for k, its in groups.items() if _tiles256(its) >= 16}
         n = sum(len(its) for its in sel.values())
         if len(sel) < 2 or n > GROUPED_MAX:
@@ -391,7 +380,7 @@ def _block_done():
     """End of one GPT-2 block's backward: with data-parallel overlap on, flush this task's
     queue every OVERLAP_BLOCKS blocks."""
     G = OVERLAP_BLOCKS[0]
-    if G <= 0 or not DEFER_WGRAD:
+    if G <= 0:
         return
     task = _task()
     n = _BLOCKS_SEEN.get(task, 0) + 1
@@ -462,7 +451,7 @@ def _wgrad(ctx, i, p, dy2, x2, defer=False):
     g = _sink(p, ctx)
     if g is None:
         return K.linear_dw(dy2, x2)
-    if defer and DEFER_WGRAD:  # dy2 and x2 must stay unmodified until the end of backward
+    if defer:  # dy2 and x2 must stay unmodified until the end of backward
         _defer_wgrad(p, g, dy2, x2)
         return None
     K.linear_dw(dy2, x2, out=g, residual=g)
@@ -477,7 +466,7 @@ def _bgrad(ctx, i, p, dy2, defer=False):
     g = _sink(p, ctx)
     if g is None:
         return K.colsum(dy2)
-    if defer and DEFER_WGRAD and dy2.shape[0] > 0 and dy2.stride(1) == 1:
+    if defer and dy2.shape[0] > 0 and dy2.stride(1) == 1:
         _defer_wgrad(p, g.view(-1), dy2, None)
         return None
     K.colsum(dy2, out=g, accumulate=True)
@@ -492,7 +481,7 @@ def _ln_bwd(ctx, iw, ib, w, b, dy2, x2, mean, rstd, dx, accumulate_dx, residual=
     gw = _sink(w, ctx) if nw else None
     gb = _sink(b, ctx) if nb else None
     if (nw or nb) and (gw is not None or not nw) and (gb is not None or not nb):
-        if DEFER_WGRAD and DEFER_LN and x2.shape[0] > 0:  # partials flushed at the end of backward
+        if x2.shape[0] > 0:  # partials flushed at the end of backward
             _, (ws, nblk) = K.layernorm_bwd(dy2, x2, w, mean, rstd, dx=dx, accumulate_dx=accumulate_dx,
                                             residual=residual, defer_wb=True)
             task = _task()
@@ -542,7 +531,7 @@ class GPTBlockFn(torch.autograd.Function):
         xn2, m2, r2 = K.layernorm_fwd(xm, ln2_w, ln2_b)
         # the c_fc epilogue stores gelu'(x) (act 3) for the backward's dGELU multiply
         hpre = torch.empty(B * T, fc_w.shape[0], dtype=BF16, device=x.device)
-        h = K.linear(xn2, fc_w, fc_b, act=1 + GELU_DERIV, pre_out=hpre)
+        h = K.linear(xn2, fc_w, fc_b, act=3, pre_out=hpre)
         out = K.linear(h, mproj_w, mproj_b, residual=xm)
         if any(ctx.needs_input_grad):  # (grad mode is off inside forward)
             ctx.save_for_backward(x2, xn1, m1, r1, qkv, y, lse, xm, xn2, m2, r2, hpre, h, ln1_w,
@@ -567,7 +556,7 @@ class GPTBlockFn(torch.autograd.Function):
         # MLP c_proj
         g[11] = _wgrad(ctx, 11, P[11], d2, h, defer=True)
         g[12] = _bgrad(ctx, 12, P[12], d2, defer=True)
-        dpre = K.linear_dx(d2, mproj_w, dact=3 if GELU_DERIV else 1, pre_in=hpre)
+        dpre = K.linear_dx(d2, mproj_w, dact=3, pre_in=hpre)
         g[9] = _wgrad(ctx, 9, P[9], dpre, xn2, defer=True)
         g[10] = _bgrad(ctx, 10, P[10], dpre, defer=True)
         dxn2 = K.linear_dx(dpre, fc_w)
@@ -705,8 +694,8 @@ class LinearFn(torch.autograd.Function):
         if drop_p > 0:
             dbr = K.dropout_mask_apply(dbr, drop_p, seed, seed_ptr=_off(dbr, drop_p))
         dx = K.linear_dx(dbr, w).view(shp) if _need(ctx, 0) else None
-        dw = _wgrad(ctx, 1, ctx.params[0], dbr, x2, defer=DEFER_BRIDGE)
-        db = _bgrad(ctx, 2, ctx.params[1], dbr, defer=DEFER_BRIDGE)
+        dw = _wgrad(ctx, 1, ctx.params[0], dbr, x2, defer=True)
+        db = _bgrad(ctx, 2, ctx.params[1], dbr, defer=True)
         return dx, dw, db, dres, dgate, None, None
 
 
@@ -719,7 +708,7 @@ class MLPFn(torch.autograd.Function):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).to(BF16).contiguous()
         hpre = torch.empty(x2.shape[0], w1.shape[0], dtype=BF16, device=x.device)
-        h = K.linear(x2, w1, b1, act=act + GELU_DERIV, pre_out=hpre)  # pre_out <- gelu'(x)
+        h = K.linear(x2, w1, b1, act=act + 2, pre_out=hpre)  # 3 tanh form / 4 erf form: pre_out <- gelu'(x)
         r2 = residual.reshape(-1, w2.shape[0]).to(BF16).contiguous() if residual is not None else None
         y = K.linear(h, w2, b2, residual=r2, drop_p=drop_p, seed=seed, seed_ptr=_off(h, drop_p))
         if any(ctx.needs_input_grad):  # (grad mode is off inside forward)
@@ -738,11 +727,11 @@ class MLPFn(torch.autograd.Function):
         if drop_p > 0:
             d2 = K.dropout_mask_apply(d2, drop_p, seed, seed_ptr=_off(d2, drop_p))
         P = ctx.params
-        dw2 = _wgrad(ctx, 3, P[3], d2, h, defer=DEFER_BRIDGE)
-        db2 = _bgrad(ctx, 4, P[4], d2, defer=DEFER_BRIDGE)
-        dpre = K.linear_dx(d2, w2, dact=3 if GELU_DERIV else act, pre_in=hpre)
-        dw1 = _wgrad(ctx, 1, P[1], dpre, x2, defer=DEFER_BRIDGE)
-        db1 = _bgrad(ctx, 2, P[2], dpre, defer=DEFER_BRIDGE)
+        dw2 = _wgrad(ctx, 3, P[3], d2, h, defer=True)
+        db2 = _bgrad(ctx, 4, P[4], d2, defer=True)
+        dpre = K.linear_dx(d2, w2, dact=3, pre_in=hpre)
+        dw1 = _wgrad(ctx, 1, P[1], dpre, x2, defer=True)
+        db1 = _bgrad(ctx, 2, P[2], dpre, defer=True)
         dx = K.linear_dx(dpre, w1).view(shp) if _need(ctx, 0) else None
         return dx, dw1, db1, dw2, db2, dres, None, None, None
 
@@ -799,8 +788,8 @@ class MHAFn(torch.autograd.Function):
         dbr = (K.dropout_mask_apply(d2, p_out, seed, seed_ptr=_off(d2, p_out)) if p_out > 0
                else d2)
         P_in_w, P_in_b, P_out_w, P_out_b = ctx.params
-        d_out_w = _wgrad(ctx, 4, P_out_w, dbr, o.view(B * Tq, C), defer=DEFER_BRIDGE)
-        d_out_b = _bgrad(ctx, 5, P_out_b, dbr, defer=DEFER_BRIDGE)
+        d_out_w = _wgrad(ctx, 4, P_out_w, dbr, o.view(B * Tq, C), defer=True)
+        d_out_b = _bgrad(ctx, 5, P_out_b, dbr, defer=True)
         do = K.linear_dx(dbr, out_w).view(B, Tq, C)
         # packed in_proj gradients: written into the sinks (accumulate) or fresh buffers
         sw = _sink(P_in_w, ctx) if _need(ctx, 2) else None
@@ -808,25 +797,22 @@ class MHAFn(torch.autograd.Function):
         din_w = torch.empty_like(in_w) if (_need(ctx, 2) and sw is None) else None
         din_b = (torch.empty(3 * C, dtype=BF16, device=d2.device)
                  if (_need(ctx, 3) and sb is None) else None)
-        tw = sw if sw is not None else din_w
         tb = sb if sb is not None else din_b
 
         # into the arena sinks the row slices are deferred like the other bridge gradients
         # (one grouped launch at the end of backward; the grad-ready hook after the last slice)
-        dfw = sw is not None and DEFER_BRIDGE and DEFER_INPROJ and DEFER_WGRAD
-        dfb = sb is not None and DEFER_BRIDGE and DEFER_INPROJ and DEFER_WGRAD
         b_deferred = [False]  # some slice went to the queue: its flush fires the grad-ready hook
 
         def wg(dy_, x_, rows):
-            if dfw:
-                _defer_wgrad(P_in_w, tw[rows], dy_, x_)
-            elif tw is not None:
-                K.linear_dw(dy_, x_, out=tw[rows], residual=tw[rows] if sw is not None else None)
+            if sw is not None:
+                _defer_wgrad(P_in_w, sw[rows], dy_, x_)
+            elif din_w is not None:
+                K.linear_dw(dy_, x_, out=din_w[rows])
 
         def bg(dy_, rows):
             # deferred under the same guard as _bgrad (rows present, unit column stride); today
             # dqkv / dqp / dkvp are fresh contiguous buffers, so the guard only protects callers
-            if dfb and dy_.shape[0] > 0 and dy_.stride(1) == 1:
+            if sb is not None and dy_.shape[0] > 0 and dy_.stride(1) == 1:
                 _defer_wgrad(P_in_b, tb[rows], dy_, None)
                 b_deferred[0] = True
             elif tb is not None:
@@ -861,8 +847,6 @@ class MHAFn(torch.autograd.Function):
                 dq_in = K.linear_dx(dqp, in_w[:C]).view(B, Tq, C)
             if _need(ctx, 1):
                 dkv_in = K.linear_dx(dkvp, in_w[C:]).view(B, Tk, C)
-        if sw is not None and not dfw:
-            _ready(P_in_w)
         if sb is not None and not b_deferred[0]:
             _ready(P_in_b)
         return dq_in, dkv_in, din_w, din_b, d_out_w, d_out_b, dres, None, None, None, None, None
@@ -926,7 +910,7 @@ def _xattn_bwd(ctx, dout, dkv, g):
     ix, iln_w, iln_b, iq_w, iq_b, ic_w, ic_b, igate = ctx.idx
     P = ctx.params
     d2 = dout.reshape(B * T, C).to(BF16).contiguous()
-    gsink = _sink(P[igate], ctx) if _need(ctx, igate) and GATE_SINK else None
+    gsink = _sink(P[igate], ctx) if _need(ctx, igate) else None
     if gsink is not None:  # added into the gate's bf16 grad in the finish kernel
         dbr = K.gate_bwd(d2, ybr, gate, grad_bf16=gsink)
         _ready(P[igate])
@@ -1170,13 +1154,10 @@ class LMHeadLossFn(torch.autograd.Function):
             else:
                 xt = x2.view(B, S, C)[:, off:off + T].reshape(B * T, C).contiguous()
             g = _sink(ctx.params[1], ctx)  # the tied wte's arena gradient: C += dl^T x
-            if g is not None and DEFER_WGRAD and DEFER_LMHEAD:
+            if g is not None:
                 # queued: the end-of-backward flush can run it in one grouped launch with the
                 # blocks' weight gradients (dl and xt stay alive in the queue until then)
                 _defer_wgrad(ctx.params[1], g, dl, xt, alpha_ptr=scale)
-            elif g is not None:
-                K.gemm(dl, xt, a_mn=True, b_mn=True, alpha_ptr=scale, out=g, residual=g)
-                _ready(ctx.params[1])
             else:
                 dw = K.gemm(dl, xt, a_mn=True, b_mn=True, alpha_ptr=scale)
         return dx, dw, None, None, None, None, None

@@ -9,7 +9,6 @@ from __future__ import annotations
 import ctypes as C
 import math
 
-import os
 
 import torch
 
@@ -96,9 +95,8 @@ def _gemm_workspace(device):
 _TK = {}
 GEMM_TICKETS = 1 << 16
 # Arrival tickets (gvl.h ABI v5) go with every gvl_gemm call; the persistent kernel's in-launch
-# two-way combine that uses them stays off unless GVL_PP3_COMBINE=1 (checked in C, gemm_plan.hip).
-# Batched weight gradients may use it (gvl_gemm_batched decides; GVL_BATCHED_SPLIT=0: never).
-BATCHED_SPLIT = os.environ.get("GVL_BATCHED_SPLIT", "1") != "0"
+# two-way combine that uses them stays off for single GEMMs (decided in C, gemm_plan.hip).
+# Batched weight gradients may use it (gvl_gemm_batched decides).
 
 
 def _gemm_tickets(device):
@@ -266,10 +264,10 @@ def gemm_batched(items, *, a_mn=False, b_mn=False, dbias=None):
             d.residual, d.ldr = out.data_ptr(), out.stride(0)
         if ws is None:
             ws = _gemm_workspace(a.device)
-            tk = _gemm_tickets(a.device) if BATCHED_SPLIT else None
+            tk = _gemm_tickets(a.device)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        if tk is not None:  # the library may split a batch that underfills the chip in two
-            d.tickets, d.ticket_count = tk.data_ptr(), tk.numel()
+        # the library may split a batch that underfills the chip in two
+        d.tickets, d.ticket_count = tk.data_ptr(), tk.numel()
 
     def call():
         if dbias is None:

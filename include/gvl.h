@@ -120,7 +120,7 @@ int gvl_gemm_batched_dbias(const gvl_gemm_desc* d, void* const* dbias, int32_t c
  * Returns 0 when launched, -1 when the problems do not qualify and nothing was launched. */
 int gvl_gemm_grouped(const gvl_gemm_desc* d, void* const* dbias, int32_t count,
                      gvl_stream_t stream);
-/* Process-wide GEMM implementation knob (benchmarking / A-B tests; env GVL_GEMM_IMPL):
+/* Process-wide GEMM implementation knob (benchmarking / A-B tests):
  * impl 3 (default) = persistent ping-pong 256x256 kernel (split-K for few tiles) where
  * the work items fill the chip, else the 128x128 LDS-DMA ring; 2 = ring / non-persistent
  * ping-pong family; 1 = LDS-DMA v2 (K % 64 == 0); 0 = register-staged kernel always.
@@ -131,8 +131,8 @@ int gvl_gemm_grouped(const gvl_gemm_desc* d, void* const* dbias, int32_t count,
  * them (and without the AGPR four-wave kernel), 12 (ABI v8, round 4) the AGPR four-wave kernel
  * (gemm_w4x.hip: 256 x 192 / 128 x 192 tiles, K-contiguous A, plain or bias + residual) where
  * it applies; 13 (ABI v10) = cfg 11 with the persistent kernel's in-launch two-way combine
- * enabled for single GEMMs (tests; otherwise only with env GVL_PP3_COMBINE=1, since the
- * callers' tickets are passed to every gvl_gemm by gvl.kernels); other cfg values route as -1.  impl 4 (the removed 64-deep quadrant-phase
+ * enabled for single GEMMs (tests; otherwise never, since the callers' tickets are passed
+ * to every gvl_gemm by gvl.kernels); other cfg values route as -1.  impl 4 (the removed 64-deep quadrant-phase
  * kernel) is rejected. */
 int gvl_gemm_tune(int32_t impl, int32_t cfg);
 /* Name of the kernel template instance gvl_gemm would launch for d (profiling: lets a

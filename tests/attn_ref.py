@@ -206,9 +206,9 @@ BWD_CLASSES = ("short<32>", "short<32,64>", "short<64>", "dq<2>+dkdv", "dq<1>+dk
 
 
 def routes(Tq, Tk, drop):
-    """(forward kernel, backward path) of gvl_attn_fwd / gvl_attn_bwd at the default GVL_ATTN_*
-    switches, restated from attention.hip (pick_groups: two query groups when Tq > 64; the
-    LDS-DMA forward needs no dropout and more than one 64-key tile)."""
+    """(forward kernel, backward path) of gvl_attn_fwd / gvl_attn_bwd, restated branch for branch
+    from attention.hip (pick_groups: two query groups when Tq > 64; the LDS-DMA forward needs no
+    dropout and more than one 64-key tile)."""
     G = 2 if Tq > 64 else 1
     if not drop and Tk > 64:
         fwd = f"dma<{G}>"

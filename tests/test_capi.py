@@ -40,6 +40,28 @@ def test_library_links_no_vendor_blas():
     assert needed and not any("blas" in ln.lower() for ln in needed), needed
 
 
+def test_library_reads_no_environment():
+    """The settled A/B switches are frozen: libgvl imports no getenv, so no routing decision can
+    depend on the environment (gvl_gemm_tune is the only handle on it)."""
+    import subprocess
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "-W", LIB],
+                         capture_output=True, text=True, check=True).stdout
+    syms = [ln.split()[-1].split("@")[0] for ln in out.splitlines() if " UND " in ln]
+    assert any(s.startswith("hip") for s in syms), syms[:8]  # (the listing is the imports)
+    assert [s for s in syms if "getenv" in s] == []
+
+
+def test_package_reads_only_the_kept_variables():
+    """The gvl package reads exactly these GVL_* variables (the library path, the documented id
+    check, and the data-parallel overlap / trace handles)."""
+    import glob
+    pat = re.compile(r"""(?:environ(?:\.get)?|getenv)\s*[\[(]\s*["'](GVL_[A-Z0-9_]+)["']""")
+    found = set()
+    for path in glob.glob(os.path.join(ROOT, "gpt2-vision-language_amd", "gvl", "*.py")):
+        found |= set(pat.findall(open(path).read()))
+    assert found == {"GVL_LIB", "GVL_CHECK_IDS", "GVL_DP_OVERLAP_BLOCKS", "GVL_TRACE_BUCKETS"}
+
+
 def test_binding_covers_header():
     from gvl import _lib
     assert sorted(_lib.SIGNATURES) == declared()

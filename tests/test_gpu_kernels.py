@@ -190,8 +190,7 @@ def test_gemm_linear_decoder_rows(cuda, K, b_mn, epi):
     A = a.to(cuda)
     B = (b if b_mn else b.t().contiguous()).to(cuda)
     name = _kernel_name(A, B, 0, b_mn, M, N, K, epi=epi)
-    if os.environ.get("GVL_W4X_128", "2") != "0":
-        assert name.startswith("gemm_w4x_kernel<128, 192"), name
+    assert name.startswith("gemm_w4x_kernel<128, 192"), name
     h = a.float() @ b.float()
     kw, ref = {}, h
     if epi == "bias_res":
@@ -538,13 +537,12 @@ W4D_EPIS = ("plain", "bias", "bias_res", "res_inplace", "drop_res")
 
 def _w4_tiles(M, N, b_mn=0, cus=256):
     """(128-row tiles?, 128 x 96 tiles?) as gemm_w4.hip's w4_use128 / w4_use96 decide (96-column
-    tiles for a K-contiguous B only, unless GVL_W4_BN96=2)."""
+    tiles for a K-contiguous B only)."""
     tn = -(-N // 128)
     t192, t128 = -(-M // 192) * tn, -(-M // 128) * tn
     r128 = t192 * 4 < cus * 3 and t128 > t192 and t128 <= cus
     t96 = -(-M // 128) * -(-N // 96)
-    mode = int(os.environ.get("GVL_W4_BN96", "1"))
-    c96 = r128 and mode != 0 and (not b_mn or mode >= 2) and t128 < t96 <= cus
+    c96 = r128 and not b_mn and t128 < t96 <= cus
     return r128, c96
 
 
@@ -554,24 +552,19 @@ def _w4_rows96(M, N, b_mn, epi, cus=256):
     r128, _ = _w4_tiles(M, N, b_mn, cus)
     tn = -(-N // 128)
     t128, t96 = -(-M // 128) * tn, -(-M // 96) * tn
-    return (r128 and b_mn and epi == "plain" and os.environ.get("GVL_W4_BM96", "1") != "0"
-            and t128 < t96 <= cus)
+    return r128 and b_mn and epi == "plain" and t128 < t96 <= cus
 
 
 def _w4_name(M, K, epi, N=768, b_mn=0):
-    """Kernel the default four-wave routing picks (GVL_W4D unset): the direct-A variant
-    (gemm_w4d.h) when K is a multiple of six 64-deep steps and the epilogue is one of its;
-    128-row tiles where 192-row ones fill under 3/4 of the chip, 128 x 96 ones (gemm_w4n_kernel)
+    """Kernel the four-wave routing picks: the direct-A variant (gemm_w4d.h) for 192-row tiles
+    when K is a multiple of six 64-deep steps and the epilogue is one of its; 128-row tiles where 192-row ones fill under 3/4 of the chip, 128 x 96 ones (gemm_w4n_kernel)
     where those fill more of it in one round."""
-    mode = os.environ.get("GVL_W4D", "1")
     r128, c96 = _w4_tiles(M, N, b_mn)
-    rows = "m" if r128 else ""
-    direct = K % 384 == 0 and epi in W4D_EPIS and mode != "0" and (mode == "2" or not rows)
-    if direct:
-        return f"gemm_w4d{rows}_kernel"
+    if not r128 and K % 384 == 0 and epi in W4D_EPIS:
+        return "gemm_w4d_kernel"
     if _w4_rows96(M, N, b_mn, epi):
         return "gemm_w4r_kernel"
-    return "gemm_w4n_kernel" if c96 else f"gemm_w4{rows}_kernel"
+    return "gemm_w4n_kernel" if c96 else ("gemm_w4m_kernel" if r128 else "gemm_w4_kernel")
 
 
 @pytest.mark.parametrize("b_mn", [0, 1])
@@ -636,8 +629,8 @@ def test_gemm_w4(cuda, b_mn, epi, M, N, K):
         _lib.lib().gvl_gemm_tune(3, -1)
     if big is not None:
         assert torch.all(big[:, N:] == 7.0) and torch.all(big[M:, :] == 7.0)
-    # 128-row tiles (gemm_w4m_kernel / gemm_w4dm_kernel) where 192-row ones would fill < 3/4
-    # of the CUs; the direct-A variant where K % 384 == 0 and its epilogue is instantiated
+    # 128-row tiles (gemm_w4m_kernel) where 192-row ones would fill < 3/4 of the CUs; else the
+    # direct-A variant where K % 384 == 0 and its epilogue is instantiated
     assert name.startswith(_w4_name(M, K, epi, N, b_mn)), name
     assert rel_err(y.float().cpu().numpy(), ref.detach().numpy()) < 8e-3
     if epi == "bias_act_d":

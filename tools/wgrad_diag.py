@@ -94,14 +94,8 @@ if os.environ.get("GVL_WGRAD_LM", "0") == "1":
     for order in ("lm_last", "lm_first"):
         its = blk + [(dl, xl, gl)] if order == "lm_last" else [(dl, xl, gl)] + blk
         dbs = blk_db + [None] if order == "lm_last" else [None] + blk_db
-        for bn in ("auto", "256", "192"):
-            if bn == "auto":
-                os.environ.pop("GVL_W4X_GR_BN", None)
-            else:
-                os.environ["GVL_W4X_GR_BN"] = bn
-            assert K.gemm_grouped(its, dbias=dbs)
-            _lib.lib().gvl_gemm_batched_kernel_name(buf, 128)
-            tg = timeit(lambda: K.gemm_grouped(its, dbias=dbs))
-            print(f"grouped x{len(its)} {order} bn={bn}: {tg:8.1f}us ({fl_sel / tg / 1e6:6.0f} TF/s)  "
-                  f"[{buf.value.decode()}]", flush=True)
-    os.environ.pop("GVL_W4X_GR_BN", None)
+        assert K.gemm_grouped(its, dbias=dbs)
+        _lib.lib().gvl_gemm_batched_kernel_name(buf, 128)
+        tg = timeit(lambda: K.gemm_grouped(its, dbias=dbs))
+        print(f"grouped x{len(its)} {order}: {tg:8.1f}us ({fl_sel / tg / 1e6:6.0f} TF/s)  "
+              f"[{buf.value.decode()}]", flush=True)
