@@ -7,6 +7,9 @@
 // value row (16-B loads, 32 rows in flight per sweep) and folds the 32 partial rows in LDS.
 // Its IND instance (gvl_attn_decode_beam, beam search) takes the cache row of every key / value
 // from an int32 table src[sequence][position]; the plain instance is unchanged by it.
+// Its GAP instances (gvl_attn_decode_ragged, prompts of different lengths in one batch) leave
+// out the keys of a per-sequence range [gap_lo[sequence], gap_hi): those are never loaded and
+// take no part in the max, the sum or the accumulation; the other two instances are unchanged.
 //
 // sample_kernel: one 1024-thread workgroup per row; the row (V <= 65536) sits in registers as
 // contiguous 64-element chunks.  softmax(logits / T) -> top-k by an 8-bit radix select on the
@@ -14,6 +17,8 @@
 // reference's sorted-cumsum prefix: every token whose preceding cumulative probability is
 // <= top_p, gpt2_linear/data.py:117-122) -> inverse-CDF draw of the caller's uniform u in
 // token-index order (block prefix scan of the per-thread kept mass).
+#include <type_traits>
+
 #include "common.h"
 #include "capi_util.h"
 #include "../../include/gvl.h"
@@ -35,10 +40,23 @@ struct DecP {
   int64_t src_ld;
 };
 
+// GAP: the skipped key range of every sequence, on top of DecP (the instances without GAP take
+// DecP itself, so their arguments are what they were).
+struct DecGapP : DecP {
+  const int32_t* gap_lo;  // per sequence; clamped into [0, gap_hi] by the kernel
+  int64_t gap_hi;
+};
+
 // IND (gvl_attn_decode_beam): the key / value of position t of sequence b come from cache row
 // src[b][t] instead of row b; everything else, the order of accumulation included, is shared.
-template <bool IND>
-__global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
+// GAP (gvl_attn_decode_ragged): a key t with glo <= t < ghi is skipped in all three loops: it
+// is not loaded (a NaN or an infinity there cannot reach the output: 0 * NaN is NaN, so a masked
+// score would not do) and its sc[t] is never written or read.  Every other key keeps its thread
+// and every value its thread group and place in the sums, so an empty gap gives the bits of the
+// instance without GAP.  A sequence with every key skipped has l == 0 and writes zeros.
+template <bool IND, bool GAP>
+__global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(
+    std::conditional_t<GAP, DecGapP, DecP> p) {
   __shared__ float qs[64];
   __shared__ float sc[DEC_MAXT];
   __shared__ float red[DEC_NT / 64];
@@ -52,8 +70,15 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   const bf16_t* kb = p.k + (IND ? 0 : b * p.k_sb) + h * 64;
   const int32_t* srow = IND ? p.src + b * p.src_ld : nullptr;
   const int rmax = (int)gridDim.y - 1;
+  int64_t glo = 0, ghi = 0;
+  if constexpr (GAP) {
+    ghi = p.gap_hi;
+    glo = min(max((int64_t)p.gap_lo[b], (int64_t)0), ghi);
+  }
   float mx = -INFINITY;
   for (int64_t t = tid; t < p.Tk; t += DEC_NT) {
+    if constexpr (GAP)
+      if (t >= glo && t < ghi) continue;
     const int64_t kr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.k_sb : 0;
     const uint4* row = reinterpret_cast<const uint4*>(kb + kr + t * p.k_st);
     float s = 0.f;
@@ -70,6 +95,8 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   mx = block_max<DEC_NT>(mx, red);
   float l = 0.f;
   for (int64_t t = tid; t < p.Tk; t += DEC_NT) {
+    if constexpr (GAP)
+      if (t >= glo && t < ghi) continue;
     const float e = __builtin_amdgcn_exp2f(sc[t] - mx);
     sc[t] = e;
     l += e;
@@ -79,6 +106,8 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
   const bf16_t* vb = p.v + (IND ? 0 : b * p.v_sb) + h * 64 + d8 * 8;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int64_t t = tg; t < p.Tk; t += 32) {
+    if constexpr (GAP)
+      if (t >= glo && t < ghi) continue;
     const int64_t vr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.v_sb : 0;
     float f[8];
     unpack8(*reinterpret_cast<const uint4*>(vb + vr + t * p.v_st), f);
@@ -93,7 +122,9 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(DecP p) {
     float s = 0.f;
 #pragma unroll
     for (int g = 0; g < 32; ++g) s += part[g][tid];
-    p.o[b * p.o_sb + h * 64 + tid] = f2bf(s / l);
+    if constexpr (GAP) s = l > 0.f ? s / l : 0.f;
+    else s = s / l;
+    p.o[b * p.o_sb + h * 64 + tid] = f2bf(s);
   }
 }
 
@@ -324,8 +355,8 @@ extern "C" int gvl_attn_decode(const void* q, int64_t q_sb, const void* k, int64
   DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
          static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
          v_sb, v_st, o_sb, scale, nullptr, 0};
-  hipLaunchKernelGGL(attn_decode_kernel<false>, dim3((unsigned)H, (unsigned)B), dim3(DEC_NT), 0,
-                     gvl::as_stream(stream), p);
+  hipLaunchKernelGGL((attn_decode_kernel<false, false>), dim3((unsigned)H, (unsigned)B),
+                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_attn_decode");
   return 0;
 }
@@ -350,9 +381,44 @@ extern "C" int gvl_attn_decode_beam(const void* q, int64_t q_sb, const void* k, 
   DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
          static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
          v_sb, v_st, o_sb, scale, src, src_ld};
-  hipLaunchKernelGGL(attn_decode_kernel<true>, dim3((unsigned)H, (unsigned)B), dim3(DEC_NT), 0,
-                     gvl::as_stream(stream), p);
+  hipLaunchKernelGGL((attn_decode_kernel<true, false>), dim3((unsigned)H, (unsigned)B),
+                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_attn_decode_beam");
+  return 0;
+}
+
+extern "C" int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k, int64_t k_sb,
+                                      int64_t k_st, const void* v, int64_t v_sb, int64_t v_st,
+                                      void* o, int64_t o_sb, int64_t B, int64_t H, int64_t Tk,
+                                      float scale, const int32_t* src, int64_t src_ld,
+                                      const int32_t* gap_lo, int64_t gap_hi,
+                                      gvl_stream_t stream) {
+  GVL_REQUIRE(q && k && v && o, "gvl_attn_decode_ragged: null buffer");
+  GVL_REQUIRE(gap_lo, "gvl_attn_decode_ragged: null gap_lo table");
+  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "gvl_attn_decode_ragged: Tk=%lld out of range (1..%d)",
+              (long long)Tk, DEC_MAXT);
+  GVL_REQUIRE(gap_hi >= 0 && gap_hi <= Tk, "gvl_attn_decode_ragged: gap_hi=%lld outside 0..Tk=%lld",
+              (long long)gap_hi, (long long)Tk);
+  GVL_REQUIRE(!src || src_ld >= Tk, "gvl_attn_decode_ragged: src_ld=%lld < Tk=%lld",
+              (long long)src_ld, (long long)Tk);
+  GVL_REQUIRE(B >= 0 && B <= 65535 && H >= 0,
+              "gvl_attn_decode_ragged: B=%lld / H=%lld out of range", (long long)B, (long long)H);
+  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
+                  gvl::aligned16(k) && gvl::aligned16(v),
+              "gvl_attn_decode_ragged: K/V rows must be 16-byte aligned");
+  if (B == 0 || H == 0) return 0;
+  DecGapP p{{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
+             static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
+             v_sb, v_st, o_sb, scale, src, src ? src_ld : 0},
+            gap_lo, gap_hi};
+  const dim3 grid((unsigned)H, (unsigned)B);
+  if (src)
+    hipLaunchKernelGGL((attn_decode_kernel<true, true>), grid, dim3(DEC_NT), 0,
+                       gvl::as_stream(stream), p);
+  else
+    hipLaunchKernelGGL((attn_decode_kernel<false, true>), grid, dim3(DEC_NT), 0,
+                       gvl::as_stream(stream), p);
+  GVL_LAUNCH_CHECK("gvl_attn_decode_ragged");
   return 0;
 }
 

@@ -6,6 +6,21 @@
 
 namespace {
 
+// o[c] = a[c] + b[c] over one row of C columns by one wave: fp32 sums, one rounding.
+GVL_DEV void emb_add_row(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b,
+                         bf16_t* __restrict__ o, int C, int lane) {
+  for (int c = lane * 8; c < C; c += 512) {
+    const uint4 u = *reinterpret_cast<const uint4*>(a + c);
+    const uint4 v = *reinterpret_cast<const uint4*>(b + c);
+    uint4 w;
+    w.x = pack2(lo_bf(u.x) + lo_bf(v.x), hi_bf(u.x) + hi_bf(v.x));
+    w.y = pack2(lo_bf(u.y) + lo_bf(v.y), hi_bf(u.y) + hi_bf(v.y));
+    w.z = pack2(lo_bf(u.z) + lo_bf(v.z), hi_bf(u.z) + hi_bf(v.z));
+    w.w = pack2(lo_bf(u.w) + lo_bf(v.w), hi_bf(u.w) + hi_bf(v.w));
+    *reinterpret_cast<uint4*>(o + c) = w;
+  }
+}
+
 // out[row(r)] = wte[idx[r]] + wpe[r % T]; row(r) = (r/T)*S + off + r%T.
 __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict__ idx,
                                                       const bf16_t* __restrict__ wte,
@@ -23,16 +38,27 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict_
   const bf16_t* a = wte + ((id >= 0 && id < V) ? id : 0) * (int64_t)C;
   const bf16_t* b = wpe + t * (int64_t)C;
   bf16_t* o = out + orow * (int64_t)C;
-  for (int c = lane * 8; c < C; c += 512) {
-    const uint4 u = *reinterpret_cast<const uint4*>(a + c);
-    const uint4 v = *reinterpret_cast<const uint4*>(b + c);
-    uint4 w;
-    w.x = pack2(lo_bf(u.x) + lo_bf(v.x), hi_bf(u.x) + hi_bf(v.x));
-    w.y = pack2(lo_bf(u.y) + lo_bf(v.y), hi_bf(u.y) + hi_bf(v.y));
-    w.z = pack2(lo_bf(u.z) + lo_bf(v.z), hi_bf(u.z) + hi_bf(v.z));
-    w.w = pack2(lo_bf(u.w) + lo_bf(v.w), hi_bf(u.w) + hi_bf(v.w));
-    *reinterpret_cast<uint4*>(o + c) = w;
-  }
+  emb_add_row(a, b, o, C, lane);
+}
+
+// out[r] = wte[idx[r]] + wpe[pos[r]]: one token per sequence, each at its own position (a decode
+// step over prompts of different lengths).  The sums and their rounding are emb_fwd_kernel's.
+// A position outside [0, n_pos) is treated as an id outside [0, V) is: it reads row 0.
+__global__ __launch_bounds__(256) void emb_fwd_pos_kernel(const int64_t* __restrict__ idx,
+                                                          const int32_t* __restrict__ pos,
+                                                          const bf16_t* __restrict__ wte,
+                                                          const bf16_t* __restrict__ wpe,
+                                                          bf16_t* __restrict__ out, int64_t n, int C,
+                                                          int64_t V, int64_t n_pos) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t id = idx[r];
+  const int64_t t = pos[r];
+  const bf16_t* a = wte + ((id >= 0 && id < V) ? id : 0) * (int64_t)C;
+  const bf16_t* b = wpe + ((t >= 0 && t < n_pos) ? t : 0) * (int64_t)C;
+  bf16_t* o = out + r * (int64_t)C;
+  emb_add_row(a, b, o, C, lane);
 }
 
 __global__ __launch_bounds__(256) void emb_bwd_kernel(const int64_t* __restrict__ idx,
@@ -437,6 +463,24 @@ extern "C" int gvl_embedding_fwd(const int64_t* idx, const void* wte, const void
                      static_cast<const bf16_t*>(wpe), static_cast<bf16_t*>(out), n_tokens, T, (int)C,
                      out_rows_per_seq, out_offset, vocab);
   GVL_LAUNCH_CHECK("gvl_embedding_fwd");
+  return 0;
+}
+
+extern "C" int gvl_embedding_fwd_pos(const int64_t* idx, const int32_t* pos, const void* wte,
+                                     const void* wpe, void* out, int64_t n_tokens, int64_t C,
+                                     int64_t vocab, int64_t n_pos, gvl_stream_t stream) {
+  GVL_REQUIRE(C > 0 && C % 8 == 0, "gvl_embedding_fwd_pos: C=%lld must be a positive multiple of 8",
+              (long long)C);
+  GVL_REQUIRE(vocab > 0 && n_pos > 0, "gvl_embedding_fwd_pos: vocab and n_pos must be > 0");
+  GVL_REQUIRE(n_tokens >= 0, "gvl_embedding_fwd_pos: n_tokens=%lld is negative",
+              (long long)n_tokens);
+  if (n_tokens == 0) return 0;
+  GVL_REQUIRE(idx && pos && wte && wpe && out, "gvl_embedding_fwd_pos: null buffer");
+  hipLaunchKernelGGL(emb_fwd_pos_kernel, dim3((unsigned)((n_tokens + 3) / 4)), dim3(256), 0,
+                     gvl::as_stream(stream), idx, pos, static_cast<const bf16_t*>(wte),
+                     static_cast<const bf16_t*>(wpe), static_cast<bf16_t*>(out), n_tokens, (int)C,
+                     vocab, n_pos);
+  GVL_LAUNCH_CHECK("gvl_embedding_fwd_pos");
   return 0;
 }
 

@@ -93,6 +93,8 @@ SIGNATURES = {
                                     c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "gvl_embedding_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
                                     c_i64, c_vp]),
+    "gvl_embedding_fwd_pos": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                        c_vp]),
     "gvl_embedding_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
                                     c_i64, c_vp]),
     "gvl_copy_rows": (C.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64,
@@ -117,6 +119,9 @@ SIGNATURES = {
                              c_vp]),
     "gvl_attn_decode_beam": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
                                        c_i64, c_i64, c_i64, c_i64, c_f32, c_vp, c_i64, c_vp]),
+    "gvl_attn_decode_ragged": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                         c_i64, c_i64, c_i64, c_i64, c_f32, c_vp, c_i64, c_vp,
+                                         c_i64, c_vp]),
     "gvl_beam_step_workspace_size": (c_i64, [c_i64, c_i32]),
     "gvl_beam_step": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32,
                                 c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -20,7 +20,17 @@ token costs one row through each block:
     (gvl_attn_decode_beam); the prefix is prefilled once per item and no cache row is copied;
   * repetition penalty, no-repeat n-gram, minimum length and bad-token bans edit each step's
     logits in place before the token choice (gvl_logits_process: one launch, a hypothesis'
-    history read through the same src table, only the few logits concerned are touched).
+    history read through the same src table, only the few logits concerned are touched);
+  * prompts of different lengths in one batch (prompt_lens): prompt_ids [B, P] is right-padded
+    and the cache stays time-aligned.  The prefill runs over all S = M + P columns as ever
+    (causality keeps the pads from the real positions), every row's i-th new token lands in
+    column S + i, so the c_attn GEMM still writes one uniform column per step, and row r attends
+    [0, M + len_r) and [S, S + i]: gvl_attn_decode_ragged skips its gap [M + len_r, S) without
+    loading it.  The first logits are gathered from each row's last real row, the new tokens take
+    positions len_r + i (gvl_embedding_fwd_pos), and the beam table, gvl_beam_step and the final
+    ids gather are untouched (t0 stays S).  Each row decodes as if it had been called alone, and
+    no output bit depends on the pad ids.  Writing row r's tokens at M + len_r + i instead would
+    need per-row GEMM output addresses.
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
@@ -50,9 +60,45 @@ def _cross_params(blk):
                 gate=bf(blk.cross_gate), H=xa.n_head)
 
 
+def check_prompt_lens(prompt_ids, prompt_lens, n_new, block_size):
+    """The real lengths of the rows of a right-padded prompt_ids [B, P] as an int64 CPU tensor
+    [B].  prompt_lens: B integers (a list, a CPU or a device tensor: one host read), each in
+    1..P, and max(len) + n_new - 1 <= block_size: the positions of the n_new - 1 tokens that are
+    fed back must exist (what step() otherwise finds out at the step that runs past them)."""
+    B, P = prompt_ids.shape
+    lens = torch.as_tensor(prompt_lens)
+    if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+        raise ValueError(f"prompt_lens must hold integers (got {lens.dtype})")
+    lens = lens.detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+    if lens.numel() != B:
+        raise ValueError(f"prompt_lens has {lens.numel()} entries for {B} prompts")
+    if B and (int(lens.min()) < 1 or int(lens.max()) > P):
+        raise ValueError(f"prompt_lens must lie in 1..P = {P} (got {int(lens.min())}.."
+                         f"{int(lens.max())})")
+    if B and int(lens.max()) + int(n_new) - 1 > block_size:
+        raise ValueError(f"a prompt of {int(lens.max())} tokens + {int(n_new)} new tokens exceeds "
+                         f"block_size {block_size}")
+    return lens
+
+
+def ragged_prompt_for_controls(prompt_ids, lens):
+    """The prompt gvl_logits_process sees for right-padded prompt_ids [B, P] with lengths lens
+    [B]: int64 [B, P], row r = P - len_r entries of -1, then prompt_ids[r, :len_r], so the real
+    tokens end where the generated ones begin.  An id outside [0, V) never indexes logits and a
+    real token never equals -1, so the bans and penalties are those of the unpadded prompt."""
+    P = prompt_ids.shape[1]
+    dev = prompt_ids.device
+    shift = (P - lens.to(device=dev, dtype=torch.int64)).view(-1, 1)
+    col = torch.arange(P, device=dev).view(1, -1)
+    real = prompt_ids.to(torch.int64).gather(1, (col - shift).clamp_(min=0))
+    return torch.where(col >= shift, real, real.new_full((), -1)).contiguous()
+
+
 class KVDecoder:
     """Prefill + one-token steps for gvl.gpt2.GPT, gvl.caption.GPT_Caption (its frozen
-    decoder) and gvl.cross_att.GPT.  Batch B; the cache holds the prefix + max_new tokens."""
+    decoder) and gvl.cross_att.GPT.  Batch B; the cache holds the prefix + max_new tokens.
+    With prompt_lens (start) the prompts are right-padded rows of different lengths: see the
+    module docstring."""
 
     def __init__(self, model, batch: int, max_new: int):
         from . import caption, cross_att
@@ -75,6 +121,11 @@ class KVDecoder:
         self.kvz = None
         self.t = 0        # positions in the cache
         self.txt0 = 0     # cache position of the first text token (caption prefix length)
+        # prompts of different lengths (prefill with lens); None: every row has P tokens
+        self.gap_lo = None  # int32 [rows], device: row r skips cache columns [gap_lo[r], gap_hi)
+        self.gap_hi = 0     # = the prefix length S
+        self.pos = None     # int32 [rows], device: the position of the next token of each row
+        self.max_len = 0    # the longest prompt (host)
 
     # ---------------------------------------------------------------- pieces
     def _ln(self, x2, wb):
@@ -95,7 +146,9 @@ class KVDecoder:
 
     def _attend(self, q, k, v, H, cross):
         """One new query per row over cached keys / values (self-attention cache, or the
-        cross-att model's projected image tokens)."""
+        cross-att model's projected image tokens: no gap there)."""
+        if self.gap_lo is not None and not cross:
+            return K.attn_decode_ragged(q, k, v, H, self.gap_lo, self.gap_hi)
         return K.attn_decode(q, k, v, H)
 
     def _alloc_cache(self, B, C, device):
@@ -114,10 +167,19 @@ class KVDecoder:
 
     # ------------------------------------------------------------------ API
     @torch.no_grad()
-    def prefill(self, x_emb):
+    def prefill(self, x_emb, lens=None):
         """x_emb [B, S, C]: the whole prefix (image tokens + prompt embeddings).  Returns the
-        logits of the last position [B, V]."""
+        logits of the last position [B, V].  lens (int64 CPU [B], from check_prompt_lens): the
+        real text length of every right-padded row; the logits are then those of each row's last
+        real position, and the steps skip the row's pad columns."""
         B, S, C = x_emb.shape
+        self.gap_lo = self.pos = None
+        if lens is not None:
+            dl = lens.to(x_emb.device)
+            self.gap_lo = (dl + self.txt0).to(torch.int32)
+            self.gap_hi = S
+            self.pos = dl.to(torch.int32)
+            self.max_len = int(lens.max())
         self.Tmax = S + self.max_new
         self.cache = self._alloc_cache(B, C, x_emb.device)
         x2 = x_emb.to(BF16).reshape(B * S, C).contiguous()
@@ -131,7 +193,11 @@ class KVDecoder:
             x2 = K.linear(y.view(B * S, C), P["aproj"][0], P["aproj"][1], residual=x2)
             x2 = self._mlp(x2, P)
         self.t = S
-        last = x2.view(B, S, C)[:, S - 1].contiguous()
+        if self.gap_lo is None:
+            last = x2.view(B, S, C)[:, S - 1].contiguous()
+        else:  # row b's last real row: b*S + gap_lo[b] - 1
+            rows = torch.arange(B, device=x2.device) * S + (self.gap_lo.long() - 1)
+            last = x2.index_select(0, rows)
         return self._logits(last)
 
     @torch.no_grad()
@@ -140,12 +206,18 @@ class KVDecoder:
         B, C, t = self.rows, self.C, self.t
         if t >= self.Tmax:
             raise ValueError("KV cache full")
-        pos = t - self.txt0
+        ragged = self.gap_lo is not None
+        # the furthest position of this step: the longest prompt's when the rows differ
+        pos = self.max_len + t - self.gap_hi if ragged else t - self.txt0
         if pos >= self.wpe.shape[0]:
             raise ValueError(f"position {pos} exceeds block_size {self.wpe.shape[0]}")
         Fn.check_index_range(ids, self.wte.shape[0], "token id")
         x = torch.empty(B, 1, C, dtype=BF16, device=ids.device)
-        K.embedding_fwd(ids.view(B, 1), self.wte, self.wpe[pos:pos + 1], x, 1, 1, 0)
+        if ragged:
+            K.embedding_fwd_pos(ids.view(B), self.pos, self.wte, self.wpe, x)
+            self.pos += 1
+        else:
+            K.embedding_fwd(ids.view(B, 1), self.wte, self.wpe[pos:pos + 1], x, 1, 1, 0)
         x2 = x.view(B, C)
         for l, P in enumerate(self.blocks):
             if self.cross is not None:
@@ -161,11 +233,16 @@ class KVDecoder:
 
     # ------------------------------------------------------- model-specific prefixes
     @torch.no_grad()
-    def start(self, prompt_ids, z=None):
+    def start(self, prompt_ids, z=None, prompt_lens=None):
         """Prefill for the model kind: text-only (GPT), [bridge(z) | text] (caption), or text
-        with the cached cross-attention keys/values of z (cross-att).  Returns logits [B, V]."""
+        with the cached cross-attention keys/values of z (cross-att).  Returns logits [B, V].
+        prompt_lens: the real lengths of the right-padded rows of prompt_ids (the pad entries
+        must be valid ids; no output depends on them)."""
         m = self.model
         self.kvz = None
+        lens = None
+        if prompt_lens is not None:
+            lens = check_prompt_lens(prompt_ids, prompt_lens, self.max_new, self.block_size)
         if self.kind == "caption":
             pt = z.unsqueeze(1) if z.dim() == 2 else z
             if m.use_cls_only:
@@ -174,7 +251,7 @@ class KVDecoder:
             M = img.shape[1]
             emb = Fn.EmbedFn.apply(prompt_ids, self.wte, self.wpe, img)
             self.txt0 = M
-            return self.prefill(emb)
+            return self.prefill(emb, lens)
         if self.kind == "cross" and z is not None:
             zp = m.transformer.vis_proj(z).to(BF16)
             Sz = zp.shape[1]
@@ -184,7 +261,7 @@ class KVDecoder:
             self.cross = None  # z=None: the gated cross-attention is skipped (model.py:159-165)
         self.txt0 = 0
         emb = Fn.EmbedFn.apply(prompt_ids, self.wte, self.wpe, None)
-        return self.prefill(emb)
+        return self.prefill(emb, lens)
 
 
 class BeamDecoder(KVDecoder):
@@ -220,19 +297,26 @@ class BeamDecoder(KVDecoder):
     def _attend(self, q, k, v, H, cross):
         if self.src is None:  # a one-token prefill of the cross-att model: B plain rows
             return super()._attend(q, k, v, H, cross)
-        return K.attn_decode_beam(q, k, v, H, self.kv_src if cross else self.src)
+        if cross:
+            return K.attn_decode_beam(q, k, v, H, self.kv_src)
+        if self.gap_lo is not None:
+            return K.attn_decode_ragged(q, k, v, H, self.gap_lo, self.gap_hi, src=self.src)
+        return K.attn_decode_beam(q, k, v, H, self.src)
 
     @torch.no_grad()
-    def prefill(self, x_emb):
+    def prefill(self, x_emb, lens=None):
         self.prefill_batch = x_emb.shape[0]
-        logits = super().prefill(x_emb)
+        logits = super().prefill(x_emb, lens)
         self.cache, self._full = self._full, None  # step() sees all R rows
+        if self.gap_lo is not None:  # per hypothesis: those of its item
+            self.gap_lo = self.gap_lo.repeat_interleave(self.K)
+            self.pos = self.pos.repeat_interleave(self.K)
         return logits
 
     @torch.no_grad()
-    def start(self, prompt_ids, z=None):
+    def start(self, prompt_ids, z=None, prompt_lens=None):
         """Prefill at batch B.  Returns the items' logits [B, V] (those of slot 0 of each)."""
-        logits = super().start(prompt_ids, z)
+        logits = super().start(prompt_ids, z, prompt_lens)
         if self.kvz is not None:
             Sz = self.kvz[0].shape[1]
             item = torch.arange(self.rows, device=logits.device, dtype=torch.int32) // self.K
@@ -270,10 +354,12 @@ def sample_next(logits, *, greedy=False, temperature=1.0, top_k=0, top_p=1.0, ge
 
 class _Controls:
     """The logits processors of generate / beam_search (gvl_logits_process): what is on, the
-    prompt as part of the penalised sequence, the bad-token list uploaded once."""
+    prompt as part of the penalised sequence (with prompt_lens: each row's real tokens, moved up
+    against the generated ones by ragged_prompt_for_controls), the bad-token list uploaded once."""
 
     def __init__(self, prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
-                 bad_tokens, penalize_prompt):
+                 bad_tokens, penalize_prompt, prompt_lens=None):
+        # prompt_lens: None or the checked lengths (check_prompt_lens)
         self.pen = float(repetition_penalty)
         self.ngram = int(no_repeat_ngram_size)
         self.eos = eos
@@ -285,7 +371,10 @@ class _Controls:
         self.always = self.pen != 1.0 or self.ngram != 0 or self.bad is not None
         self.prompt = None
         if penalize_prompt and (self.pen != 1.0 or self.ngram != 0):
-            self.prompt = prompt_ids.to(torch.int64).contiguous()
+            if prompt_lens is None:
+                self.prompt = prompt_ids.to(torch.int64).contiguous()
+            else:
+                self.prompt = ragged_prompt_for_controls(prompt_ids, prompt_lens)
 
     def apply(self, logits, hist, step, **kw):
         ban_eos = step < self.min_new
@@ -299,9 +388,14 @@ class _Controls:
 def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0, top_k=0,
              top_p=1.0, generator=None, return_logits=False, eos=None, return_lengths=False,
              repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-             penalize_prompt=True):
+             penalize_prompt=True, prompt_lens=None):
     """KV-cached decode of n_new tokens after prompt_ids [B, P].  greedy: argmax (first max);
     else temperature / top-k / top-p sampling with `generator` (a CUDA torch.Generator).
+
+    prompt_lens (B integers: a list or a tensor): prompt_ids is right-padded and row r's prompt
+    is prompt_ids[r, :prompt_lens[r]], 1 <= prompt_lens[r] <= P.  Row r then decodes as if it had
+    been called alone with that prompt, the penalised sequence included; the pad entries must be
+    valid ids and no output depends on them.  max(prompt_lens) + n_new - 1 <= block_size.
 
     Before the token choice (and before temperature / top-k / top-p, Hugging Face's order) each
     step's logits pass gvl_logits_process: repetition_penalty (Hugging Face's rule, once per
@@ -316,10 +410,13 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
     tokens up to and including eos, n_new for a row that never ended."""
     B = prompt_ids.shape[0]
     dec = KVDecoder(model, B, n_new)
-    logits = dec.start(prompt_ids, z)
+    lens = None
+    if prompt_lens is not None:
+        lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
+    logits = dec.start(prompt_ids, z, lens)
     dev = logits.device
     ctl = _Controls(prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
-                    bad_tokens, penalize_prompt)
+                    bad_tokens, penalize_prompt, lens)
     hist = torch.empty(n_new, B, dtype=torch.int64, device=dev)
     lengths = torch.full((B,), n_new, dtype=torch.int32, device=dev)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -353,9 +450,10 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
 @torch.no_grad()
 def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
                 return_all=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                min_new_tokens=0, bad_tokens=None, penalize_prompt=True):
+                min_new_tokens=0, bad_tokens=None, penalize_prompt=True, prompt_lens=None):
     """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
-    hypotheses per item.  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
+    hypotheses per item (prompt_lens: right-padded prompts of different lengths, as in
+    generate()).  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
     tokens; hypotheses are ranked by raw * n ** -length_penalty (n = its length, end token
     included), ties to the lower parent slot and then the lower token id (gvl_beam_step).  One
     that emits `eos` is finished and competes with its final score; the search ends after n_new
@@ -373,10 +471,13 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     B, Kb = prompt_ids.shape[0], num_beams
     R = B * Kb
     dec = BeamDecoder(model, B, Kb, n_new)
-    first = dec.start(prompt_ids, z)
+    lens = None
+    if prompt_lens is not None:
+        lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
+    first = dec.start(prompt_ids, z, lens)
     dev, V, t0 = first.device, first.shape[1], dec.t
     ctl = _Controls(prompt_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
-                    bad_tokens, penalize_prompt)
+                    bad_tokens, penalize_prompt, lens)
     logits = torch.empty(R, V, dtype=first.dtype, device=dev)
     logits.view(B, Kb, V)[:, 0] = first  # slots 1.. start empty (score -inf): never read
     len_norm = torch.arange(n_new + 2, dtype=torch.float32).clamp_(min=1.0).pow_(

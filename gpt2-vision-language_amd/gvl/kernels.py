@@ -485,6 +485,40 @@ def attn_decode_beam(q, k, v, H, src, out=None, scale=None):
     return out
 
 
+def attn_decode_ragged(q, k, v, H, gap_lo, gap_hi, src=None, out=None, scale=None):
+    """attn_decode (src None) or attn_decode_beam (src given) that leaves out the keys
+    [gap_lo[r], gap_hi) of sequence r (include/gvl.h gvl_attn_decode_ragged): the pad columns
+    of a batch of right-padded prompts in a time-aligned cache.  gap_lo int32 [rows of q] on the
+    device; 0 <= gap_hi <= Tk.  -> o [rows of q, H*64]."""
+    _dev(q, k, v, gap_lo, src)
+    R, Tk = q.shape[0], k.shape[1]
+    if (gap_lo.dtype != torch.int32 or gap_lo.dim() != 1 or gap_lo.numel() != R or
+            not gap_lo.is_contiguous()):
+        raise ValueError("gvl: gap_lo must be a contiguous int32 [rows of q] vector")
+    gap_hi = int(gap_hi)
+    if not 0 <= gap_hi <= Tk:
+        raise ValueError(f"gvl: gap_hi = {gap_hi} outside 0..Tk = {Tk}")
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R:
+            raise ValueError("gvl: src must be an int32 [rows of q, >= Tk] table")
+        if k.shape[0] > R or v.shape[0] > R:
+            raise ValueError("gvl: the cache has more rows than q; src could not name them")
+    elif k.shape[0] != R or v.shape[0] != R:
+        raise ValueError("gvl: without src the cache must have one row per row of q")
+    if out is None:
+        out = torch.empty(R, H * 64, dtype=BF16, device=q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(64)
+    _lib.check(_L().gvl_attn_decode_ragged(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
+                                           k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
+                                           out.data_ptr(), out.stride(0), R, H, Tk, float(scale),
+                                           _p(src), 0 if src is None else src.stride(0),
+                                           gap_lo.data_ptr(), gap_hi, _stream()),
+               "gvl_attn_decode_ragged")
+    return out
+
+
 def beam_step(logits2, score, flen, len_norm, src, K, step, eos, t0, out=None, workspace=None):
     """One beam-search step for B items x K beams (include/gvl.h gvl_beam_step).  logits2
     [B*K, V] bf16 / fp32; score fp32 [B*K]; flen int32 [B*K]; len_norm fp32 [>= step + 2]; src
@@ -731,6 +765,28 @@ def embedding_fwd(idx, wte, wpe, out, T, out_rows_per_seq, out_offset):
     _lib.check(_L().gvl_embedding_fwd(idx.data_ptr(), wte.data_ptr(), wpe.data_ptr(),
                                       out.data_ptr(), idx.numel(), T, C_, V, out_rows_per_seq,
                                       out_offset, _stream()), "gvl_embedding_fwd")
+    return out
+
+
+def embedding_fwd_pos(idx, pos, wte, wpe, out=None):
+    """out[r] = wte[idx[r]] + wpe[pos[r]] (include/gvl.h gvl_embedding_fwd_pos): idx int64 [n],
+    pos int32 [n] on the device, out bf16 [n, C] contiguous.  -> out."""
+    _dev(idx, pos, wte, wpe, out)
+    n = idx.numel()
+    V, C_ = wte.shape
+    if idx.dtype != torch.int64 or pos.dtype != torch.int32 or pos.numel() != n:
+        raise ValueError("gvl: embedding_fwd_pos takes int64 ids and as many int32 positions")
+    if wte.dtype != BF16 or wpe.dtype != BF16 or wpe.shape[1] != C_ or \
+            not (wte.is_contiguous() and wpe.is_contiguous()):
+        raise ValueError("gvl: embedding_fwd_pos takes contiguous bf16 wte [V, C] and wpe [T, C]")
+    if out is None:
+        out = torch.empty(n, C_, dtype=BF16, device=idx.device)
+    elif out.dtype != BF16 or out.numel() != n * C_ or not out.is_contiguous():
+        raise ValueError("gvl: embedding_fwd_pos writes a contiguous bf16 [n, C] tensor")
+    idx, pos = idx.contiguous(), pos.contiguous()
+    _lib.check(_L().gvl_embedding_fwd_pos(idx.data_ptr(), pos.data_ptr(), wte.data_ptr(),
+                                          wpe.data_ptr(), out.data_ptr(), n, C_, V, wpe.shape[0],
+                                          _stream()), "gvl_embedding_fwd_pos")
     return out
 
 

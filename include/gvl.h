@@ -254,6 +254,16 @@ int gvl_cross_entropy(const void* logits, int64_t ldl, int64_t rows, int64_t voc
 int gvl_embedding_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out,
                       int64_t n_tokens, int64_t T, int64_t C, int64_t vocab,
                       int64_t out_rows_per_seq, int64_t out_offset, gvl_stream_t stream);
+/* One token per sequence, each at its own position (a decode step over prompts of different
+ * lengths): out[r] = wte[idx[r]] + wpe[pos[r]] for r < n_tokens, out rows contiguous
+ * (C elements apart), pos int32 [n_tokens] on the device, n_pos = rows of wpe.  The same sums
+ * and rounding as gvl_embedding_fwd: row r holds the bits of gvl_embedding_fwd called on token r
+ * alone with T = 1 and wpe + pos[r]*C.  A position outside [0, n_pos) is treated as an id
+ * outside [0, vocab) is: never dereferenced, it reads row 0; callers check both on the host.
+ * C % 8 == 0.  Added at ABI v14 without a version bump: a new symbol, nothing existing changes. */
+int gvl_embedding_fwd_pos(const int64_t* idx, const int32_t* pos, const void* wte,
+                          const void* wpe, void* out, int64_t n_tokens, int64_t C, int64_t vocab,
+                          int64_t n_pos, gvl_stream_t stream);
 /* Backward: fp32 scatter-add into dwte_acc [V][C] and dwpe_acc [T][C] (caller zeroes). */
 int gvl_embedding_bwd(const int64_t* idx, const void* dout, float* dwte_acc, float* dwpe_acc,
                       int64_t n_tokens, int64_t T, int64_t C, int64_t vocab,
@@ -383,6 +393,33 @@ int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B
                   int32_t step, int32_t eos, int64_t t0, const int32_t* src_in, int64_t src_ld,
                   int64_t* tok_out, int32_t* parent_out, float* score_out, int32_t* flen_out,
                   int32_t* src_out, void* workspace, gvl_stream_t stream);
+
+/* Decoding a batch of prompts of different lengths.  Added at ABI v14 without a version bump,
+ * like the beam entry points: a new symbol, nothing existing changes.
+ *
+ * gvl_attn_decode_ragged: gvl_attn_decode_beam (src may be null: then the plain layout of
+ * gvl_attn_decode, key t of sequence r in cache row r) that leaves out, per sequence r, the
+ * keys of the range [gap_lo[r], gap_hi): gap_lo int32 [B] on the device, one entry per sequence
+ * (per row of q), gap_hi the same for all.  The cache stays time-aligned: right-padded prompts
+ * are prefilled into columns [0, gap_hi) and every sequence's i-th generated token goes to
+ * column gap_hi + i, so sequence r, whose prefix has gap_lo[r] real columns, attends
+ * [0, gap_lo[r]) and [gap_hi, Tk).
+ *   A key inside the gap is never loaded, neither k nor v, and takes no part in the maximum, the
+ *   sum or the accumulation: whatever those cache entries hold, a NaN or an infinity included,
+ *   no output bit depends on it.
+ *   The kernel clamps gap_lo[r] into [0, gap_hi], so a bad table cannot misbehave.
+ *   A sequence with every key inside the gap (gap_lo[r] <= 0 and gap_hi == Tk) writes zeros.
+ *   Every key and value outside the gap is handled by the thread, and summed in the place, it
+ *   has in gvl_attn_decode: with an empty gap (gap_lo[r] == gap_hi) the output has the bits of
+ *   gvl_attn_decode (src null) or gvl_attn_decode_beam (src given).
+ * Limits as there (Tk in 1..4096, 16-byte-aligned rows, B <= 65535; src_ld >= Tk when src is
+ * given), and 0 <= gap_hi <= Tk, gap_lo non-null: checked on the host before the launch (-1 and
+ * gvl_last_error naming the argument). */
+int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st,
+                           const void* v, int64_t v_sb, int64_t v_st, void* o, int64_t o_sb,
+                           int64_t B, int64_t H, int64_t Tk, float scale, const int32_t* src,
+                           int64_t src_ld, const int32_t* gap_lo, int64_t gap_hi,
+                           gvl_stream_t stream);
 
 /* Logits processors: repetition penalty, no-repeat n-gram, end-token and bad-token bans, applied
  * in place between a decoder step and gvl_sample / gvl_beam_step.  Added at ABI v14 without a
