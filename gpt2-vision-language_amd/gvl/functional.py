@@ -376,6 +376,12 @@ def _defer_wgrad(p, g, dy2, x2, alpha_ptr=None):
     _queue_flush(task)
 
 
+def _queued(p):
+    """True while a weight gradient of p queued by the current backward awaits its flush."""
+    task = _task()
+    return any(e[0] == task and e[1] is p for e in _PENDING)
+
+
 def _block_done():
     """End of one GPT-2 block's backward: with data-parallel overlap on, flush this task's
     queue every OVERLAP_BLOCKS blocks."""
@@ -449,6 +455,11 @@ def _wgrad(ctx, i, p, dy2, x2, defer=False):
     if not _need(ctx, i):
         return None
     g = _sink(p, ctx)
+    if dy2.shape[0] == 0:  # an empty batch adds nothing (the GEMM routes take no K = 0)
+        if g is None:
+            return torch.zeros(dy2.shape[1], x2.shape[1], dtype=BF16, device=dy2.device)
+        _ready(p)
+        return None
     if g is None:
         return K.linear_dw(dy2, x2)
     if defer:  # dy2 and x2 must stay unmodified until the end of backward
@@ -499,8 +510,9 @@ def _ln_bwd(ctx, iw, ib, w, b, dy2, x2, mean, rstd, dx, accumulate_dx, residual=
                 _ready(p)
         return None, None
     C = x2.shape[1]
-    dw = torch.empty(C, dtype=BF16, device=x2.device) if nw else None
-    db = torch.empty(C, dtype=BF16, device=x2.device) if nb else None
+    new = torch.empty if x2.shape[0] > 0 else torch.zeros  # no rows: the kernel writes nothing
+    dw = new(C, dtype=BF16, device=x2.device) if nw else None
+    db = new(C, dtype=BF16, device=x2.device) if nb else None
     K.layernorm_bwd(dy2, x2, w, mean, rstd, dx=dx, accumulate_dx=accumulate_dx, dw=dw, db=db,
                     residual=residual)
     return dw, db
@@ -803,9 +815,15 @@ class MHAFn(torch.autograd.Function):
         # (one grouped launch at the end of backward; the grad-ready hook after the last slice)
         b_deferred = [False]  # some slice went to the queue: its flush fires the grad-ready hook
 
+        w_deferred = [False]
+
         def wg(dy_, x_, rows):
-            if sw is not None:
+            if dy_.shape[0] == 0:  # an empty batch adds nothing (the GEMM routes take no K = 0)
+                if din_w is not None:
+                    din_w[rows].zero_()
+            elif sw is not None:
                 _defer_wgrad(P_in_w, sw[rows], dy_, x_)
+                w_deferred[0] = True
             elif din_w is not None:
                 K.linear_dw(dy_, x_, out=din_w[rows])
 
@@ -849,6 +867,8 @@ class MHAFn(torch.autograd.Function):
                 dkv_in = K.linear_dx(dkvp, in_w[C:]).view(B, Tk, C)
         if sb is not None and not b_deferred[0]:
             _ready(P_in_b)
+        if sw is not None and not w_deferred[0]:
+            _ready(P_in_w)
         return dq_in, dkv_in, din_w, din_b, d_out_w, d_out_b, dres, None, None, None, None, None
 
 
@@ -1086,7 +1106,10 @@ class EmbedFn(torch.autograd.Function):
                 torch.zeros(P, C, dtype=BF16, device=dout.device) if _need(ctx, 2) else None)
             K.embedding_bwd_det(idx, dout, tte, tpe, T, S, M, C, V)
             if gte is not None:
-                _ready(wte)
+                # the tied lm_head's queued weight gradient adds into the same buffer at the end
+                # of this backward: its flush then notifies once, with the gradient final
+                if not _queued(wte):
+                    _ready(wte)
             elif tte is not None:
                 dwte = tte if dt_te == BF16 else tte.to(dt_te)
             if gpe is not None:
