@@ -7,7 +7,8 @@ Drop-in module APIs:
 Runtime:
     gvl.optim (fused AdamW + clip), gvl.dist (bucketed RCCL all-reduce), gvl.train (the
     grad-accumulation DP step), gvl.generate (greedy decode), gvl.decode (KV-cached sampling and
-    beam search; gvl.beam_search is gvl.decode.beam_search), gvl.score (log-probabilities, ranks
+    beam search, speculative decoding; gvl.beam_search and gvl.speculative_generate are
+    gvl.decode's), gvl.score (log-probabilities, ranks
     and multiple-choice predictions of given text; gvl.evaluate_hellaswag, gvl.most_likely_row),
     gvl.kernels (C-ABI wrappers).
 All compute goes through libgvl.so (include/gvl.h); importing a module that needs it on a
@@ -21,7 +22,7 @@ PACKAGE_DIR = _os.path.dirname(_os.path.abspath(__file__))
 
 # KV-cached decoding (gvl.decode), resolved on first use so that `import gvl` stays light.
 # (decode.generate is not re-exported: gvl.generate is the full-recompute greedy module.)
-_DECODE_NAMES = ("beam_search", "KVDecoder", "BeamDecoder")
+_DECODE_NAMES = ("beam_search", "speculative_generate", "KVDecoder", "BeamDecoder")
 # Scoring of given text (gvl.score; gvl.score.score is the function behind the module's name).
 _SCORE_NAMES = ("most_likely_row", "evaluate_hellaswag", "Score")
 

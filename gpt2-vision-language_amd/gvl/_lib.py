@@ -122,6 +122,12 @@ SIGNATURES = {
     "gvl_attn_decode_ragged": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
                                          c_i64, c_i64, c_i64, c_i64, c_f32, c_vp, c_i64, c_vp,
                                          c_i64, c_vp]),
+    "gvl_attn_decode_multi": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                        c_i64, c_f32, c_vp]),
+    "gvl_ngram_draft": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                  c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "gvl_spec_accept": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "gvl_beam_step_workspace_size": (c_i64, [c_i64, c_i32]),
     "gvl_beam_step": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32,
                                 c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -31,6 +31,19 @@ token costs one row through each block:
     ids gather are untouched (t0 stays S).  Each row decodes as if it had been called alone, and
     no output bit depends on the pad ids.  Writing row r's tokens at M + len_r + i instead would
     need per-row GEMM output addresses.
+  * speculative decoding (KVDecoder.step_multi, speculative_generate): Q = draft_len + 1 tokens
+    per row per decoder pass.  Rows accept different numbers of drafted tokens, so here the cache
+    is compacted, not time-aligned: row r holds kv_len[r] columns (int32 on the device), the
+    c_attn GEMM of a pass writes a contiguous [B, Q, 3C] buffer, and gvl_attn_decode_multi lets
+    query j of row r attend the cache below kv_len[r] and the buffer's rows 0..j, copying the
+    new k / v into cache[r, kv_len[r] + j] in the same launch (no per-row GEMM address, no
+    scatter; what a pass wrote and the accept step did not keep is overwritten by the next).
+    Query j has the bits of gvl_attn_decode at Tk = kv_len[r] + j + 1.  The draft is a lookup of
+    the row's last n-gram in its own prompt + output (gvl_ngram_draft) or the caller's
+    draft_ids; gvl_spec_accept compares it with the tokens gvl_sample chose and advances n,
+    kv_len, pos and the output on the device.  After start(..., prompt_lens) row r begins at
+    kv_len = M + len_r, pos = len_r: its tokens overwrite its pad columns and the gap arrays go
+    unused.  step(), BeamDecoder and the ragged path are as they were.
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
@@ -126,18 +139,23 @@ class KVDecoder:
         self.gap_hi = 0     # = the prefix length S
         self.pos = None     # int32 [rows], device: the position of the next token of each row
         self.max_len = 0    # the longest prompt (host)
+        self.slack = 0      # extra cache columns past prefix + max_new (step_multi: Q of them)
 
     # ---------------------------------------------------------------- pieces
     def _ln(self, x2, wb):
         return K.layernorm_fwd(x2, wb[0], wb[1], stats=False)[0]
 
-    def _cross(self, l, x2, S):
-        """x + tanh(g) * c_proj(attn(q_proj(ln_x x), kv_proj(z_proj))) for S new rows."""
+    def _cross(self, l, x2, S, src=None):
+        """x + tanh(g) * c_proj(attn(q_proj(ln_x x), kv_proj(z_proj))) for S new rows.
+        src (step_multi): int32 [rows of x2, image tokens], the kvz row of each row of x2; the
+        rows then go through the one-query kernel, as the rows of step() do."""
         P = self.cross[l]
         kvz = self.kvz[l]
         q = K.linear(self._ln(x2, P["ln"]), *P["q"])
         C = self.C
-        if S == 1:
+        if src is not None:
+            y = K.attn_decode_beam(q, kvz[:, :, :C], kvz[:, :, C:], P["H"], src)
+        elif S == 1:
             y = self._attend(q, kvz[:, :, :C], kvz[:, :, C:], P["H"], True)
         else:
             y = K.attn_fwd(q.view(self.B, S, C), kvz[:, :, :C], kvz[:, :, C:], P["H"], False)[0]
@@ -180,7 +198,7 @@ class KVDecoder:
             self.gap_hi = S
             self.pos = dl.to(torch.int32)
             self.max_len = int(lens.max())
-        self.Tmax = S + self.max_new
+        self.Tmax = S + self.max_new + self.slack
         self.cache = self._alloc_cache(B, C, x_emb.device)
         x2 = x_emb.to(BF16).reshape(B * S, C).contiguous()
         for l, P in enumerate(self.blocks):
@@ -229,6 +247,40 @@ class KVDecoder:
             x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
             x2 = self._mlp(x2, P)
         self.t = t + 1
+        return self._logits(x2)
+
+    @torch.no_grad()
+    def step_multi(self, ids, kv_len, pos):
+        """Append Q tokens per sequence at per-sequence cache lengths (ids [B, Q], 1 <= Q <= 8;
+        kv_len, pos int32 [B] on the device, owned by the caller) and return the logits of all of
+        them [B*Q, V], row b*Q + j following token j of sequence b.  Token j of sequence b goes
+        to cache column kv_len[b] + j and takes position min(pos[b] + j, block_size - 1); the
+        caller keeps kv_len[b] + Q <= Tmax (KVDecoder.slack = Q before start()) and decides
+        afterwards how many of the Q columns count (gvl_spec_accept): the next call overwrites
+        the rest.  After start(prompt_ids, z, prompt_lens) sequence r begins at
+        kv_len = txt0 + len_r and pos = len_r (its new tokens overwrite its pad columns; gap_lo,
+        gap_hi and self.t go unused on this path)."""
+        B, C = self.rows, self.C
+        Q = ids.shape[1]
+        if ids.shape[0] != B or not 1 <= Q <= 8:
+            raise ValueError(f"step_multi takes ids [{B}, 1..8] (got {tuple(ids.shape)})")
+        if Q > self.Tmax:
+            raise ValueError("KV cache full")
+        Fn.check_index_range(ids, self.wte.shape[0], "token id")
+        at = pos.view(B, 1) + torch.arange(Q, dtype=torch.int32, device=ids.device)
+        at = at.clamp_(max=self.block_size - 1).reshape(B * Q)
+        x2 = K.embedding_fwd_pos(ids.reshape(B * Q), at, self.wte, self.wpe)
+        kv_src = None
+        if self.cross is not None:  # row b*Q + j reads the projected image tokens of sequence b
+            seq = torch.arange(B * Q, dtype=torch.int32, device=ids.device) // Q
+            kv_src = seq.view(-1, 1).expand(B * Q, self.kvz[0].shape[1]).contiguous()
+        for l, P in enumerate(self.blocks):
+            if self.cross is not None:
+                x2 = self._cross(l, x2, Q, kv_src)
+            qkv = K.linear(self._ln(x2, P["ln1"]), *P["attn"])
+            y = K.attn_decode_multi(qkv.view(B, Q, 3 * C), self.cache[l], kv_len, P["H"])
+            x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
+            x2 = self._mlp(x2, P)
         return self._logits(x2)
 
     # ------------------------------------------------------- model-specific prefixes
@@ -445,6 +497,107 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
     if return_lengths:
         out.append(lengths)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+@torch.no_grad()
+def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram=3,
+                         draft_ids=None, greedy=False, temperature=1.0, top_k=0, top_p=1.0,
+                         generator=None, eos=None, prompt_lens=None, return_lengths=False,
+                         return_stats=False):
+    """generate() with several tokens per decoder pass: draft draft_len (1..7) tokens per row,
+    feed [last token, draft] through KVDecoder.step_multi, choose a token from every one of the
+    B * (draft_len + 1) logits rows with gvl_sample and keep, per row, the drafted tokens the
+    chosen ones confirm plus the first chosen token that differs (gvl_spec_accept).
+
+    The draft is the continuation of the most recent earlier occurrence of the row's last
+    `ngram` (1..4) tokens in its prompt + output, falling back to shorter suffixes
+    (gvl_ngram_draft); draft_ids int [B, n_new] overrides it where >= 0: draft_ids[b, i] is the
+    guess for new token i of row b.  A guess of -1 is fed as id 0 and never accepted.
+
+    The draft is deterministic, so draw-and-compare is exact: new token i of row b is drawn with
+    u[i, b] from the logits that follow the accepted tokens, whatever was drafted.  u is n_new
+    successive torch.rand(B, generator=...) made up front, the uniforms generate() consumes: with
+    the same seed both aim at the same tokens (they differ only where the bf16 logits of a
+    B * (draft_len + 1)-row pass and of a B-row pass round a choice differently).  greedy:
+    top_k = 1, u = 0.  eos, prompt_lens, return_lengths: as in generate().  No logits
+    processors, return_logits or beams here.
+
+    One host read per round (n.min(), to stop once every row is done).  Returns ids
+    [B, n_new], then if asked lengths [B] int32, then if asked stats: dict(steps = rounds of
+    token choice: one on the prefill's logits, then one per decoder pass (passes = steps - 1),
+    drafted / accepted = int32 [B]: guesses made, and guesses that reached the output)."""
+    if prompt_ids.dim() != 2 or prompt_ids.shape[0] < 1 or prompt_ids.shape[1] < 1:
+        raise ValueError("prompt_ids must be [B, P] with B, P >= 1")
+    B, P = prompt_ids.shape
+    n_new, draft_len, ngram = int(n_new), int(draft_len), int(ngram)
+    if n_new < 1:
+        raise ValueError(f"n_new={n_new}: at least 1")
+    if not 1 <= draft_len <= 7:
+        raise ValueError(f"draft_len={draft_len}: 1..7 supported")
+    if not 1 <= ngram <= 4:
+        raise ValueError(f"ngram={ngram}: 1..4 supported")
+    if not greedy and not (temperature > 0 and 0 < top_p <= 1 and top_k >= 0):
+        raise ValueError("temperature > 0, 0 < top_p <= 1 and top_k >= 0 required")
+    if draft_ids is not None:
+        draft_ids = torch.as_tensor(draft_ids)
+        if (tuple(draft_ids.shape) != (B, n_new) or draft_ids.is_floating_point() or
+                draft_ids.is_complex() or draft_ids.dtype == torch.bool):
+            raise ValueError(f"draft_ids must be integers [B, n_new] = [{B}, {n_new}] "
+                             f"(got {draft_ids.dtype} {tuple(draft_ids.shape)})")
+    Q = draft_len + 1
+    dec = KVDecoder(model, B, n_new)
+    dec.slack = Q
+    if prompt_lens is not None:
+        lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
+    else:
+        lens = None
+        if P + n_new - 1 > dec.block_size:
+            raise ValueError(f"a prompt of {P} tokens + {n_new} new tokens exceeds block_size "
+                             f"{dec.block_size}")
+    if P + n_new > 4096:
+        raise ValueError(f"prompt + new tokens = {P + n_new} exceeds 4096")
+    logits = dec.start(prompt_ids, z, lens)
+    dev = logits.device
+    if dec.t + n_new + Q > 4096:
+        raise ValueError(f"prefix {dec.t} + {n_new} new tokens + {Q} exceeds 4096 cache columns")
+    i32 = dict(dtype=torch.int32, device=dev)
+    if greedy:
+        temperature, top_k, top_p = 1.0, 1, 1.0
+        u = torch.zeros(B, n_new, dtype=torch.float32, device=dev)
+    else:
+        u = torch.stack([torch.rand(B, generator=generator, device=dev, dtype=torch.float32)
+                         for _ in range(n_new)], dim=1)  # u[b, i]: row b's new token i
+    prompt = prompt_ids.to(device=dev, dtype=torch.int64).contiguous()
+    given = None if draft_ids is None else draft_ids.to(device=dev, dtype=torch.int64).contiguous()
+    plen = torch.full((B,), P, **i32) if lens is None else lens.to(**i32)
+    # The first round takes the prefill's logits as a pass of one row: it moves the state by one
+    # like any accepted token, so it starts one short of where start() left each row.
+    kv_len = plen + (dec.txt0 - 1)
+    pos = plen - 1
+    n = torch.zeros(B, **i32)
+    lengths = torch.full((B,), n_new, **i32)
+    drafted, accepted = torch.zeros(B, **i32), torch.zeros(B, **i32)
+    last = torch.zeros(B, dtype=torch.int64, device=dev)
+    out = torch.zeros(B, n_new, dtype=torch.int64, device=dev)
+    x = K.sample(logits, u[:, 0].contiguous(), temperature, top_k, top_p)
+    K.spec_accept(x.view(B, 1), None, n, kv_len, pos, lengths, last, out, eos)
+    steps = 1
+    slot = torch.arange(Q, device=dev)
+    while int(n.min()) < n_new:
+        draft = K.ngram_draft(prompt, plen, out, n, ngram, draft_len, given=given)
+        ids = torch.cat([last.view(B, 1), draft.clamp(min=0)], dim=1)
+        logits = dec.step_multi(ids, kv_len, pos)
+        uq = u.gather(1, (n.long().view(B, 1) + slot).clamp_(max=n_new - 1))
+        x = K.sample(logits, uq.reshape(B * Q), temperature, top_k, top_p)
+        K.spec_accept(x.view(B, Q), draft, n, kv_len, pos, lengths, last, out, eos, drafted,
+                      accepted)
+        steps += 1
+    res = [out]
+    if return_lengths:
+        res.append(lengths)
+    if return_stats:
+        res.append(dict(steps=steps, passes=steps - 1, drafted=drafted, accepted=accepted))
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 @torch.no_grad()

@@ -519,6 +519,104 @@ def attn_decode_ragged(q, k, v, H, gap_lo, gap_hi, src=None, out=None, scale=Non
     return out
 
 
+def _i32_vec(t, rows, name):
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != rows or not t.is_contiguous():
+        raise ValueError(f"gvl: {name} must be a contiguous int32 [{rows}] vector")
+
+
+def _ld(t):
+    """Row stride of a row-major [rows, cols] tensor (one row: torch may report any)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def attn_decode_multi(qkv, cache, kv_len, H, out=None, scale=None):
+    """Q new queries per sequence at per-sequence cache lengths, the K/V append fused
+    (include/gvl.h gvl_attn_decode_multi).  qkv bf16 [B, Q, 3C] contiguous (this step's c_attn
+    output, C = H*64); cache bf16 [B, Tmax, 3C] with contiguous rows; kv_len int32 [B] on the
+    device.  Query j of sequence b attends positions [0, kv_len[b] + j] and its k / v land in
+    cache[b, kv_len[b] + j].  -> o [B*Q, C]."""
+    _dev(qkv, cache, kv_len)
+    if qkv.dim() != 3 or cache.dim() != 3:
+        raise ValueError("gvl: attn_decode_multi takes qkv [B, Q, 3C] and cache [B, Tmax, 3C]")
+    B, Q, C3 = qkv.shape
+    C = H * 64
+    if qkv.dtype != BF16 or cache.dtype != BF16 or C3 != 3 * C or not qkv.is_contiguous():
+        raise ValueError("gvl: qkv must be a contiguous bf16 [B, Q, 3 * H * 64] tensor")
+    if (cache.shape[0] != B or cache.shape[2] != C3 or cache.stride(2) != 1 or
+            cache.stride(1) != C3):
+        raise ValueError("gvl: cache must be [B, Tmax, 3C] with contiguous rows")
+    _i32_vec(kv_len, B, "kv_len")
+    if out is None:
+        out = torch.empty(B * Q, C, dtype=BF16, device=qkv.device)
+    elif out.dtype != BF16 or out.shape != (B * Q, C) or out.stride(1) != 1:
+        raise ValueError("gvl: attn_decode_multi writes a bf16 [B*Q, C] row-major tensor")
+    if scale is None:
+        scale = 1.0 / math.sqrt(64)
+    _lib.check(_L().gvl_attn_decode_multi(qkv.data_ptr(), cache.data_ptr(), cache.stride(0),
+                                          cache.shape[1], kv_len.data_ptr(), out.data_ptr(),
+                                          out.stride(0), B, H, Q, float(scale), _stream()),
+               "gvl_attn_decode_multi")
+    return out
+
+
+def ngram_draft(prompt, plen, emitted, n, ngram, D, given=None, out=None):
+    """Prompt-lookup draft (include/gvl.h gvl_ngram_draft): prompt int64 [B, P], plen int32 [B],
+    emitted int64 [B, n_new] of which row b holds n[b] tokens (n int32 [B]), given optional int64
+    [B, n_new] (-1: none).  -> draft int64 [B, D], -1 where there is no guess."""
+    _dev(prompt, plen, emitted, n, given)
+    _rowmajor(prompt, "prompt")
+    _rowmajor(emitted, "emitted")
+    B, P = prompt.shape
+    n_new = emitted.shape[1]
+    if prompt.dtype != torch.int64 or emitted.dtype != torch.int64 or emitted.shape[0] != B:
+        raise ValueError("gvl: ngram_draft takes int64 prompt [B, P] and emitted [B, n_new]")
+    _i32_vec(plen, B, "plen")
+    _i32_vec(n, B, "n")
+    if given is not None:
+        _rowmajor(given, "given")
+        if given.dtype != torch.int64 or given.shape != (B, n_new):
+            raise ValueError("gvl: given must be an int64 [B, n_new] tensor")
+    if out is None:
+        out = torch.empty(B, int(D), dtype=torch.int64, device=prompt.device)
+    elif out.dtype != torch.int64 or out.shape != (B, int(D)) or not out.is_contiguous():
+        raise ValueError("gvl: ngram_draft writes a contiguous int64 [B, D] tensor")
+    _lib.check(_L().gvl_ngram_draft(_p(prompt) if P > 0 else None, _ld(prompt), P,
+                                    plen.data_ptr(), emitted.data_ptr(), _ld(emitted),
+                                    n.data_ptr(), n_new, _p(given),
+                                    0 if given is None else _ld(given), B, int(ngram), int(D),
+                                    out.data_ptr(), _stream()), "gvl_ngram_draft")
+    return out
+
+
+def spec_accept(x, draft, n, kv_len, pos, lengths, last, out, eos=None, drafted=None,
+                accepted=None):
+    """Accept the drafted tokens the chosen ones confirm and advance the per-sequence state, all
+    on the device (include/gvl.h gvl_spec_accept).  x int64 [B, Q]; draft int64 [B, Q - 1] (None
+    with Q = 1); n, kv_len, pos, lengths int32 [B]; last int64 [B]; out int64 [B, n_new];
+    drafted / accepted: optional int32 [B] counters."""
+    _dev(x, draft, n, kv_len, pos, lengths, last, out, drafted, accepted)
+    if x.dim() != 2 or x.dtype != torch.int64 or not x.is_contiguous():
+        raise ValueError("gvl: spec_accept takes a contiguous int64 x [B, Q]")
+    B, Q = x.shape
+    if Q > 1 and (draft is None or draft.dtype != torch.int64 or draft.shape != (B, Q - 1) or
+                  not draft.is_contiguous()):
+        raise ValueError("gvl: draft must be a contiguous int64 [B, Q - 1] tensor")
+    for t, name in ((n, "n"), (kv_len, "kv_len"), (pos, "pos"), (lengths, "lengths")):
+        _i32_vec(t, B, name)
+    for t, name in ((drafted, "drafted"), (accepted, "accepted")):
+        if t is not None:
+            _i32_vec(t, B, name)
+    _rowmajor(out, "out")
+    if (out.dtype != torch.int64 or out.shape[0] != B or last.dtype != torch.int64 or
+            last.numel() != B or not last.is_contiguous()):
+        raise ValueError("gvl: spec_accept takes int64 out [B, n_new] and last [B]")
+    _lib.check(_L().gvl_spec_accept(x.data_ptr(), _p(draft) if Q > 1 else None, B, Q, n.data_ptr(),
+                                    kv_len.data_ptr(), pos.data_ptr(), lengths.data_ptr(),
+                                    last.data_ptr(), out.data_ptr(), _ld(out), out.shape[1],
+                                    -1 if eos is None else int(eos), _p(drafted), _p(accepted),
+                                    _stream()), "gvl_spec_accept")
+
+
 def beam_step(logits2, score, flen, len_norm, src, K, step, eos, t0, out=None, workspace=None):
     """One beam-search step for B items x K beams (include/gvl.h gvl_beam_step).  logits2
     [B*K, V] bf16 / fp32; score fp32 [B*K]; flen int32 [B*K]; len_norm fp32 [>= step + 2]; src

@@ -421,6 +421,63 @@ int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k, int64_t k
                            int64_t src_ld, const int32_t* gap_lo, int64_t gap_hi,
                            gvl_stream_t stream);
 
+/* Speculative decoding: draft a few tokens per sequence, verify all of them in one KV-cached
+ * decoder pass.  Added at ABI v14 without a version bump, like the beam and ragged entry points:
+ * new symbols, nothing existing changes.
+ *
+ * gvl_attn_decode_multi: Q (1..8) new queries per sequence at per-sequence cache lengths, with
+ * the K/V append fused.  qkv is this step's contiguous c_attn output [B, Q, 3C] (C = H*64; q at
+ * columns [0, C), k at [C, 2C), v at [2C, 3C)), cache the packed per-layer cache [B, Tmax, 3C]
+ * (rows 3C apart, sequences cache_sb apart), kv_len int32 [B] on the device, o [B*Q, C] with rows
+ * o_ld apart.  With L = kv_len[b] clamped into [0, min(Tmax, 4096) - Q], query j of sequence b
+ * sits at position L + j and attends positions [0, L + j]: a key or value at t < L is read from
+ * cache[b, t], one at t >= L from qkv[b, t - L].  The launch also copies the k and v columns of
+ * qkv[b, j] into cache[b, L + j] for every j < Q.
+ *   Bit property: query j's output has exactly the bits of gvl_attn_decode with Tk = L + j + 1 on
+ *   a cache that holds the same values: every key keeps its thread and every value its thread
+ *   group and place in the sums.
+ *   Nothing in the launch reads the cache at or past L, so the append races with no load and no
+ *   separate scatter is needed.  Cache columns from L + Q on, the q columns of the cache and,
+ *   for query j, the qkv rows of later queries are never loaded: a NaN there reaches no output
+ *   bit.  Cache elements outside the k and v columns of [L, L + Q) are never written.
+ * Callers keep kv_len[b] + Q <= min(Tmax, 4096); the clamp only makes a bad table harmless.
+ *
+ * gvl_ngram_draft ("prompt lookup"): sequence b is s = prompt[b, :plen[b]] (int64 [B, P], rows
+ * prompt_ld apart; plen int32 [B], clamped into [0, P]) followed by its n[b] emitted tokens
+ * emitted[b, :n[b]] (int64, rows emitted_ld >= n_new apart; n int32 [B]); L = plen[b] + n[b],
+ * P + n_new <= 4096.  For g = ngram, ngram - 1, ..., 1 (1 <= ngram <= 4) find the largest i with
+ * i + g <= L - 1 and s[i..i+g) == s[L-g..L); the first g with a match wins and
+ * draft[b, j] = s[i + g + j] for j < D (1 <= D <= 7) while i + g + j < L.  Every other entry is
+ * -1: no guess.  Slot j guesses emitted[b, n[b] + j], the token after next for j = 1 and so on.
+ * given (optional int64 [B, n_new], rows given_ld apart) overrides: where n[b] + j < n_new and
+ * given[b, n[b] + j] >= 0, that is the draft for slot j.  A sequence with n[b] >= n_new (done)
+ * gets -1 throughout.  Ids are compared as int32.  draft is int64 [B, D], contiguous.
+ *
+ * gvl_spec_accept: x int64 [B, Q] holds the token chosen from each of the Q logits rows of a
+ * sequence (row j: after feeding [last, draft[0..j))), draft int64 [B, Q - 1] (null with Q = 1).
+ * State, all on the device: n, kv_len, pos, lengths int32 [B]; last int64 [B] (the next token to
+ * feed); out int64 [B, n_new] (rows out_ld apart).  eos < 0: no end token.  For n[b] < n_new:
+ *   a = the count of leading j < Q - 1 with draft[b, j] == x[b, j]; m = min(a + 1, n_new - n[b]);
+ *   if x[b, e] == eos for some e < m, the first such e gives m = e + 1, lengths[b] = n[b] + m,
+ *   out[b, n[b] + m ..) = eos and n[b] = n_new (done); else n[b] += m.  In both cases
+ *   out[b, n[b] .. n[b] + m) = x[b, :m] (the old n), kv_len[b] += m, pos[b] += m and
+ *   last[b] = x[b, m - 1].  drafted[b] += the count of draft[b, j] >= 0, accepted[b] += m - 1
+ *   (the drafted tokens that reached the output); either may be null.
+ * A sequence with n[b] >= n_new keeps every bit of its state.  One thread per sequence, no host
+ * involvement.  All three check their arguments on the host before the launch (-1 and
+ * gvl_last_error naming the argument). */
+int gvl_attn_decode_multi(const void* qkv, void* cache, int64_t cache_sb, int64_t Tmax,
+                          const int32_t* kv_len, void* o, int64_t o_ld, int64_t B, int64_t H,
+                          int64_t Q, float scale, gvl_stream_t stream);
+int gvl_ngram_draft(const int64_t* prompt, int64_t prompt_ld, int64_t P, const int32_t* plen,
+                    const int64_t* emitted, int64_t emitted_ld, const int32_t* n, int64_t n_new,
+                    const int64_t* given, int64_t given_ld, int64_t B, int32_t ngram, int32_t D,
+                    int64_t* draft, gvl_stream_t stream);
+int gvl_spec_accept(const int64_t* x, const int64_t* draft, int64_t B, int32_t Q, int32_t* n,
+                    int32_t* kv_len, int32_t* pos, int32_t* lengths, int64_t* last, int64_t* out,
+                    int64_t out_ld, int64_t n_new, int64_t eos, int32_t* drafted,
+                    int32_t* accepted, gvl_stream_t stream);
+
 /* Logits processors: repetition penalty, no-repeat n-gram, end-token and bad-token bans, applied
  * in place between a decoder step and gvl_sample / gvl_beam_step.  Added at ABI v14 without a
  * version bump, like the beam entry points: a new symbol, nothing existing changes.
