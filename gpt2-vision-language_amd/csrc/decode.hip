@@ -1,10 +1,8 @@
 // Incremental decoding: single-query attention over a KV cache and a fused
 // temperature / top-k / top-p sampler.  Both are latency-bound (one new token per sequence).
 //
-// attn_decode_kernel: one 256-thread workgroup per (head, sequence).  Pass 1 scores every
-// cached key against the new query (one key per thread, 8 x 16-B loads of its 64-dim row) into
-// an LDS score array, block max/sum in fp32; pass 2 accumulates p_t * v_t with 8 threads per
-// value row (16-B loads, 32 rows in flight per sweep) and folds the 32 partial rows in LDS.
+// attn_decode_kernel: one 256-thread workgroup per (head, sequence) runs attn_decode_body
+// (attn_decode.h, which describes the passes) on a strided cache.
 // Its IND instance (gvl_attn_decode_beam, beam search) takes the cache row of every key / value
 // from an int32 table src[sequence][position]; the plain instance is unchanged by it.
 // Its GAP instances (gvl_attn_decode_ragged, prompts of different lengths in one batch) leave
@@ -19,15 +17,11 @@
 // token-index order (block prefix scan of the per-thread kept mass).
 #include <type_traits>
 
-#include "common.h"
+#include "attn_decode.h"
 #include "capi_util.h"
 #include "../../include/gvl.h"
 
 namespace {
-
-constexpr int DEC_NT = 256;
-constexpr int DEC_MAXT = 4096;
-constexpr float DEC_L2E = 1.4426950408889634f;
 
 struct DecP {
   const bf16_t* q;
@@ -47,85 +41,44 @@ struct DecGapP : DecP {
   int64_t gap_hi;
 };
 
+// The KV policy (attn_decode.h) of a strided cache, for head h of sequence b.
 // IND (gvl_attn_decode_beam): the key / value of position t of sequence b come from cache row
-// src[b][t] instead of row b; everything else, the order of accumulation included, is shared.
-// GAP (gvl_attn_decode_ragged): a key t with glo <= t < ghi is skipped in all three loops: it
-// is not loaded (a NaN or an infinity there cannot reach the output: 0 * NaN is NaN, so a masked
-// score would not do) and its sc[t] is never written or read.  Every other key keeps its thread
-// and every value its thread group and place in the sums, so an empty gap gives the bits of the
-// instance without GAP.  A sequence with every key skipped has l == 0 and writes zeros.
+// src[b][t], clamped into the cache, instead of row b.
+// GAP (gvl_attn_decode_ragged): a key t with glo <= t < ghi is skipped: it is not loaded (a NaN
+// or an infinity there cannot reach the output: 0 * NaN is NaN, so a masked score would not do).
+// Every other key keeps its thread and every value its thread group and place in the sums, so an
+// empty gap gives the bits of the instance without GAP.  A sequence with every key skipped has
+// l == 0 and writes zeros.
+template <bool IND, bool GAP>
+struct CacheKV {
+  static constexpr bool may_be_empty = GAP;
+  const bf16_t* kb;  // the head's columns of cache row b (IND: of row 0)
+  const bf16_t* vb;
+  int64_t k_sb, k_st, v_sb, v_st;
+  const int32_t* srow;
+  int rmax;
+  int64_t glo, ghi;
+  GVL_DEV CacheKV(const DecP& p, int h, int b)
+      : kb(p.k + (IND ? 0 : b * p.k_sb) + h * 64), vb(p.v + (IND ? 0 : b * p.v_sb) + h * 64),
+        k_sb(p.k_sb), k_st(p.k_st), v_sb(p.v_sb), v_st(p.v_st),
+        srow(IND ? p.src + b * p.src_ld : nullptr), rmax((int)gridDim.y - 1), glo(0), ghi(0) {}
+  GVL_DEV void prologue(int) const {}
+  GVL_DEV bool skip(int64_t t) const { return GAP && t >= glo && t < ghi; }
+  GVL_DEV int64_t row(int64_t t) const { return IND ? (int64_t)min(max(srow[t], 0), rmax) : 0; }
+  GVL_DEV const bf16_t* key(int64_t t) const { return kb + row(t) * k_sb + t * k_st; }
+  GVL_DEV const bf16_t* value(int64_t t) const { return vb + row(t) * v_sb + t * v_st; }
+};
+
 template <bool IND, bool GAP>
 __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(
     std::conditional_t<GAP, DecGapP, DecP> p) {
-  __shared__ float qs[64];
-  __shared__ float sc[DEC_MAXT];
-  __shared__ float red[DEC_NT / 64];
-  __shared__ float part[32][65];
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  if (tid < 64) qs[tid] = bf2f(p.q[b * p.q_sb + h * 64 + tid]) * (p.scale * DEC_L2E);
-  __syncthreads();
-  float q[64];
-#pragma unroll
-  for (int d = 0; d < 64; ++d) q[d] = qs[d];
-  const bf16_t* kb = p.k + (IND ? 0 : b * p.k_sb) + h * 64;
-  const int32_t* srow = IND ? p.src + b * p.src_ld : nullptr;
-  const int rmax = (int)gridDim.y - 1;
-  int64_t glo = 0, ghi = 0;
+  const int h = blockIdx.x, b = blockIdx.y;
+  CacheKV<IND, GAP> kv(p, h, b);
   if constexpr (GAP) {
-    ghi = p.gap_hi;
-    glo = min(max((int64_t)p.gap_lo[b], (int64_t)0), ghi);
+    kv.ghi = p.gap_hi;
+    kv.glo = min(max((int64_t)p.gap_lo[b], (int64_t)0), kv.ghi);
   }
-  float mx = -INFINITY;
-  for (int64_t t = tid; t < p.Tk; t += DEC_NT) {
-    if constexpr (GAP)
-      if (t >= glo && t < ghi) continue;
-    const int64_t kr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.k_sb : 0;
-    const uint4* row = reinterpret_cast<const uint4*>(kb + kr + t * p.k_st);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      float f[8];
-      unpack8(row[c], f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s = fmaf(q[8 * c + j], f[j], s);
-    }
-    sc[t] = s;
-    mx = fmaxf(mx, s);
-  }
-  mx = block_max<DEC_NT>(mx, red);
-  float l = 0.f;
-  for (int64_t t = tid; t < p.Tk; t += DEC_NT) {
-    if constexpr (GAP)
-      if (t >= glo && t < ghi) continue;
-    const float e = __builtin_amdgcn_exp2f(sc[t] - mx);
-    sc[t] = e;
-    l += e;
-  }
-  l = block_sum<DEC_NT>(l, red);  // (its barriers also publish sc[])
-  const int d8 = tid & 7, tg = tid >> 3;
-  const bf16_t* vb = p.v + (IND ? 0 : b * p.v_sb) + h * 64 + d8 * 8;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t t = tg; t < p.Tk; t += 32) {
-    if constexpr (GAP)
-      if (t >= glo && t < ghi) continue;
-    const int64_t vr = IND ? (int64_t)min(max(srow[t], 0), rmax) * p.v_sb : 0;
-    float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(vb + vr + t * p.v_st), f);
-    const float w = sc[t];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = fmaf(w, f[j], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) part[tg][d8 * 8 + j] = acc[j];
-  __syncthreads();
-  if (tid < 64) {
-    float s = 0.f;
-#pragma unroll
-    for (int g = 0; g < 32; ++g) s += part[g][tid];
-    if constexpr (GAP) s = l > 0.f ? s / l : 0.f;
-    else s = s / l;
-    p.o[b * p.o_sb + h * 64 + tid] = f2bf(s);
-  }
+  attn_decode_body(p.q + b * p.q_sb + h * 64, p.scale, p.Tk, kv, p.o + b * p.o_sb + h * 64);
 }
 
 constexpr int SMP_NT = 1024;
@@ -341,24 +294,41 @@ __global__ __launch_bounds__(SMP_NT) void sample_kernel(SampP p) {
 
 }  // namespace
 
+// What the three cache entry points require alike; `fn` names the caller in the message.
+static int check_cached(const char* fn, const void* q, const void* k, int64_t k_sb, int64_t k_st,
+                        const void* v, int64_t v_sb, int64_t v_st, const void* o, int64_t B,
+                        int64_t H, int64_t Tk) {
+  GVL_REQUIRE(q && k && v && o, "%s: null buffer", fn);
+  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "%s: Tk=%lld out of range (1..%d)", fn, (long long)Tk,
+              DEC_MAXT);
+  GVL_REQUIRE(B >= 0 && B <= 65535 && H >= 0, "%s: B=%lld / H=%lld out of range", fn,
+              (long long)B, (long long)H);
+  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
+                  gvl::aligned16(k) && gvl::aligned16(v),
+              "%s: K/V rows must be 16-byte aligned", fn);
+  return 0;
+}
+
+template <bool IND, bool GAP>
+static int launch_cached(const char* fn, const std::conditional_t<GAP, DecGapP, DecP>& p,
+                         int64_t B, int64_t H, gvl_stream_t stream) {
+  if (B == 0 || H == 0) return 0;
+  hipLaunchKernelGGL((attn_decode_kernel<IND, GAP>), dim3((unsigned)H, (unsigned)B),
+                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
+  GVL_LAUNCH_CHECK(fn);
+  return 0;
+}
+
 extern "C" int gvl_attn_decode(const void* q, int64_t q_sb, const void* k, int64_t k_sb,
                                int64_t k_st, const void* v, int64_t v_sb, int64_t v_st, void* o,
                                int64_t o_sb, int64_t B, int64_t H, int64_t Tk, float scale,
                                gvl_stream_t stream) {
-  GVL_REQUIRE(q && k && v && o, "gvl_attn_decode: null buffer");
-  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "gvl_attn_decode: Tk=%lld out of range (1..%d)",
-              (long long)Tk, DEC_MAXT);
-  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
-                  gvl::aligned16(k) && gvl::aligned16(v),
-              "gvl_attn_decode: K/V rows must be 16-byte aligned");
-  if (B == 0 || H == 0) return 0;
+  const char* fn = "gvl_attn_decode";
+  if (check_cached(fn, q, k, k_sb, k_st, v, v_sb, v_st, o, B, H, Tk)) return -1;
   DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
          static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
          v_sb, v_st, o_sb, scale, nullptr, 0};
-  hipLaunchKernelGGL((attn_decode_kernel<false, false>), dim3((unsigned)H, (unsigned)B),
-                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
-  GVL_LAUNCH_CHECK("gvl_attn_decode");
-  return 0;
+  return launch_cached<false, false>(fn, p, B, H, stream);
 }
 
 extern "C" int gvl_attn_decode_beam(const void* q, int64_t q_sb, const void* k, int64_t k_sb,
@@ -366,25 +336,15 @@ extern "C" int gvl_attn_decode_beam(const void* q, int64_t q_sb, const void* k, 
                                     void* o, int64_t o_sb, int64_t B, int64_t H, int64_t Tk,
                                     float scale, const int32_t* src, int64_t src_ld,
                                     gvl_stream_t stream) {
-  GVL_REQUIRE(q && k && v && o, "gvl_attn_decode_beam: null buffer");
+  const char* fn = "gvl_attn_decode_beam";
+  if (check_cached(fn, q, k, k_sb, k_st, v, v_sb, v_st, o, B, H, Tk)) return -1;
   GVL_REQUIRE(src, "gvl_attn_decode_beam: null src table");
-  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "gvl_attn_decode_beam: Tk=%lld out of range (1..%d)",
-              (long long)Tk, DEC_MAXT);
   GVL_REQUIRE(src_ld >= Tk, "gvl_attn_decode_beam: src_ld=%lld < Tk=%lld", (long long)src_ld,
               (long long)Tk);
-  GVL_REQUIRE(B >= 0 && B <= 65535 && H >= 0, "gvl_attn_decode_beam: B=%lld / H=%lld out of range",
-              (long long)B, (long long)H);
-  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
-                  gvl::aligned16(k) && gvl::aligned16(v),
-              "gvl_attn_decode_beam: K/V rows must be 16-byte aligned");
-  if (B == 0 || H == 0) return 0;
   DecP p{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
          static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
          v_sb, v_st, o_sb, scale, src, src_ld};
-  hipLaunchKernelGGL((attn_decode_kernel<true, false>), dim3((unsigned)H, (unsigned)B),
-                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
-  GVL_LAUNCH_CHECK("gvl_attn_decode_beam");
-  return 0;
+  return launch_cached<true, false>(fn, p, B, H, stream);
 }
 
 extern "C" int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k, int64_t k_sb,
@@ -393,33 +353,19 @@ extern "C" int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k
                                       float scale, const int32_t* src, int64_t src_ld,
                                       const int32_t* gap_lo, int64_t gap_hi,
                                       gvl_stream_t stream) {
-  GVL_REQUIRE(q && k && v && o, "gvl_attn_decode_ragged: null buffer");
+  const char* fn = "gvl_attn_decode_ragged";
+  if (check_cached(fn, q, k, k_sb, k_st, v, v_sb, v_st, o, B, H, Tk)) return -1;
   GVL_REQUIRE(gap_lo, "gvl_attn_decode_ragged: null gap_lo table");
-  GVL_REQUIRE(Tk > 0 && Tk <= DEC_MAXT, "gvl_attn_decode_ragged: Tk=%lld out of range (1..%d)",
-              (long long)Tk, DEC_MAXT);
   GVL_REQUIRE(gap_hi >= 0 && gap_hi <= Tk, "gvl_attn_decode_ragged: gap_hi=%lld outside 0..Tk=%lld",
               (long long)gap_hi, (long long)Tk);
   GVL_REQUIRE(!src || src_ld >= Tk, "gvl_attn_decode_ragged: src_ld=%lld < Tk=%lld",
               (long long)src_ld, (long long)Tk);
-  GVL_REQUIRE(B >= 0 && B <= 65535 && H >= 0,
-              "gvl_attn_decode_ragged: B=%lld / H=%lld out of range", (long long)B, (long long)H);
-  GVL_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 &&
-                  gvl::aligned16(k) && gvl::aligned16(v),
-              "gvl_attn_decode_ragged: K/V rows must be 16-byte aligned");
-  if (B == 0 || H == 0) return 0;
   DecGapP p{{static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k),
              static_cast<const bf16_t*>(v), static_cast<bf16_t*>(o), Tk, q_sb, k_sb, k_st,
              v_sb, v_st, o_sb, scale, src, src ? src_ld : 0},
             gap_lo, gap_hi};
-  const dim3 grid((unsigned)H, (unsigned)B);
-  if (src)
-    hipLaunchKernelGGL((attn_decode_kernel<true, true>), grid, dim3(DEC_NT), 0,
-                       gvl::as_stream(stream), p);
-  else
-    hipLaunchKernelGGL((attn_decode_kernel<false, true>), grid, dim3(DEC_NT), 0,
-                       gvl::as_stream(stream), p);
-  GVL_LAUNCH_CHECK("gvl_attn_decode_ragged");
-  return 0;
+  return src ? launch_cached<true, true>(fn, p, B, H, stream)
+             : launch_cached<false, true>(fn, p, B, H, stream);
 }
 
 extern "C" int gvl_sample(const void* logits, int64_t ld, int32_t logits_fp32, int64_t rows,

@@ -3,13 +3,11 @@
 //
 // attn_decode_multi_kernel: Q new queries per sequence at per-sequence cache lengths, the K/V
 // append fused.  One 256-thread workgroup per (head, sequence, query), the query on gridDim.z.
-// It is attn_decode_kernel (decode.hip) statement for statement: the same key per thread, the
-// same 8 threads per value row and 32 rows per sweep, the same reductions.  Only the address of
-// a key / value differs: position t < kv_len comes from the cache, position t >= kv_len from
-// row t - kv_len of this step's c_attn output.  So query j has exactly the bits of
-// gvl_attn_decode with Tk = kv_len + j + 1 on a cache that holds the same values.  The
-// workgroup of query j also copies its head's k and v of row j into cache[kv_len + j]; nothing
-// in the launch reads the cache at or past kv_len, so the append races with no load.
+// It runs attn_decode_body (attn_decode.h) with the append policy: position t < kv_len comes
+// from the cache, position t >= kv_len from row t - kv_len of this step's c_attn output, and
+// the workgroup of query j copies its head's k and v of row j into cache[kv_len + j] before
+// the first barrier.  Every load of the cache in the launch is at a position below kv_len and
+// every store at or past it, so the append races with no load.
 //
 // ngram_draft_kernel: one 256-thread workgroup per sequence; the sequence (prompt + emitted
 // tokens, <= 4096) sits in LDS and every thread tests candidate starts for the longest suffix
@@ -17,16 +15,13 @@
 //
 // spec_accept_kernel: one thread per sequence compares the chosen tokens with the draft and
 // advances the per-sequence state on the device.
-#include "common.h"
+#include "attn_decode.h"
 #include "capi_util.h"
 #include "../../include/gvl.h"
 
 namespace {
 
-constexpr int SPD_NT = 256;
-constexpr int SPD_MAXT = 4096;
 constexpr int SPD_MAXQ = 8;
-constexpr float SPD_L2E = 1.4426950408889634f;
 
 struct MultiP {
   const bf16_t* qkv;  // [B, Q, 3C] contiguous
@@ -38,75 +33,40 @@ struct MultiP {
   float scale;
 };
 
-__global__ __launch_bounds__(SPD_NT) void attn_decode_multi_kernel(MultiP p) {
-  __shared__ float qs[64];
-  __shared__ float sc[SPD_MAXT];
-  __shared__ float red[SPD_NT / 64];
-  __shared__ float part[32][65];
-  const int h = blockIdx.x, b = blockIdx.y, jq = blockIdx.z, tid = threadIdx.x;
+// The KV policy (attn_decode.h) of query jq of a sequence with `len` cached positions: position
+// t < len is row t of the cache, position t >= len is row t - len of this step's qkv.
+struct AppendKV {
+  static constexpr bool may_be_empty = false;  // a query always attends itself
+  bf16_t* cb;        // the sequence's cache rows
+  const bf16_t* nw;  // this step's rows of the sequence
+  int64_t len, C3, koff, voff;  // the head's k / v columns within a row
+  int jq;
+  GVL_DEV void prologue(int tid) const {  // append: 8 x 16 B of k, 8 x 16 B of v
+    if (tid >= 64 && tid < 80) {
+      const int c = tid - 64;
+      const int64_t off = (c < 8 ? koff : voff) + (c & 7) * 8;
+      *reinterpret_cast<uint4*>(cb + (len + jq) * C3 + off) =
+          *reinterpret_cast<const uint4*>(nw + jq * C3 + off);
+    }
+  }
+  GVL_DEV bool skip(int64_t) const { return false; }
+  GVL_DEV const bf16_t* row(int64_t t) const {
+    return t < len ? cb + t * C3 : nw + (t - len) * C3;
+  }
+  GVL_DEV const bf16_t* key(int64_t t) const { return row(t) + koff; }
+  GVL_DEV const bf16_t* value(int64_t t) const { return row(t) + voff; }
+};
+
+__global__ __launch_bounds__(DEC_NT) void attn_decode_multi_kernel(MultiP p) {
+  const int h = blockIdx.x, b = blockIdx.y, jq = blockIdx.z;
   const int64_t C3 = 3 * p.C;
   // the cached length, clamped so that neither the append nor sc[] can leave its array
-  const int64_t lmax = min(p.Tmax, (int64_t)SPD_MAXT) - p.Q;
+  const int64_t lmax = min(p.Tmax, (int64_t)DEC_MAXT) - p.Q;
   const int64_t len = min(max((int64_t)p.kv_len[b], (int64_t)0), lmax);
-  const int64_t Tk = len + jq + 1;
-  const bf16_t* nw = p.qkv + (int64_t)b * p.Q * C3;  // this step's rows of the sequence
-  bf16_t* cb = p.cache + b * p.cache_sb;
-  if (tid < 64) qs[tid] = bf2f(nw[jq * C3 + h * 64 + tid]) * (p.scale * SPD_L2E);
-  if (tid >= 64 && tid < 80) {  // append: 8 x 16 B of k, 8 x 16 B of v
-    const int c = tid - 64;
-    const int64_t off = (c < 8 ? p.C : 2 * p.C) + h * 64 + (c & 7) * 8;
-    *reinterpret_cast<uint4*>(cb + (len + jq) * C3 + off) =
-        *reinterpret_cast<const uint4*>(nw + jq * C3 + off);
-  }
-  __syncthreads();
-  float q[64];
-#pragma unroll
-  for (int d = 0; d < 64; ++d) q[d] = qs[d];
-  const int64_t koff = p.C + h * 64;
-  float mx = -INFINITY;
-  for (int64_t t = tid; t < Tk; t += SPD_NT) {
-    const bf16_t* kr = t < len ? cb + t * C3 : nw + (t - len) * C3;
-    const uint4* row = reinterpret_cast<const uint4*>(kr + koff);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      float f[8];
-      unpack8(row[c], f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s = fmaf(q[8 * c + j], f[j], s);
-    }
-    sc[t] = s;
-    mx = fmaxf(mx, s);
-  }
-  mx = block_max<SPD_NT>(mx, red);
-  float l = 0.f;
-  for (int64_t t = tid; t < Tk; t += SPD_NT) {
-    const float e = __builtin_amdgcn_exp2f(sc[t] - mx);
-    sc[t] = e;
-    l += e;
-  }
-  l = block_sum<SPD_NT>(l, red);  // (its barriers also publish sc[])
-  const int d8 = tid & 7, tg = tid >> 3;
-  const int64_t voff = 2 * p.C + h * 64 + d8 * 8;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t t = tg; t < Tk; t += 32) {
-    const bf16_t* vr = t < len ? cb + t * C3 : nw + (t - len) * C3;
-    float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(vr + voff), f);
-    const float w = sc[t];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = fmaf(w, f[j], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) part[tg][d8 * 8 + j] = acc[j];
-  __syncthreads();
-  if (tid < 64) {
-    float s = 0.f;
-#pragma unroll
-    for (int g = 0; g < 32; ++g) s += part[g][tid];
-    s = s / l;
-    p.o[((int64_t)b * p.Q + jq) * p.o_ld + h * 64 + tid] = f2bf(s);
-  }
+  const bf16_t* nw = p.qkv + (int64_t)b * p.Q * C3;
+  const AppendKV kv{p.cache + b * p.cache_sb, nw, len, C3, p.C + h * 64, 2 * p.C + h * 64, jq};
+  attn_decode_body(nw + jq * C3 + h * 64, p.scale, len + jq + 1, kv,
+                   p.o + ((int64_t)b * p.Q + jq) * p.o_ld + h * 64);
 }
 
 struct DraftP {
@@ -124,15 +84,15 @@ GVL_DEV int32_t id32(int64_t v) {  // ids are compared as int32; one outside it 
   return (int32_t)min(max(v, (int64_t)INT32_MIN), (int64_t)INT32_MAX);
 }
 
-__global__ __launch_bounds__(SPD_NT) void ngram_draft_kernel(DraftP p) {
-  __shared__ int32_t s[SPD_MAXT];
+__global__ __launch_bounds__(DEC_NT) void ngram_draft_kernel(DraftP p) {
+  __shared__ int32_t s[DEC_MAXT];
   __shared__ int best;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int pl = min(max(p.plen[b], 0), p.P);
   const int nb = min(max(p.n[b], 0), p.n_new);
-  const int L = pl + nb;  // <= P + n_new <= SPD_MAXT (host check)
+  const int L = pl + nb;  // <= P + n_new <= DEC_MAXT (host check)
   const bool live = nb < p.n_new;
-  for (int t = tid; t < L; t += SPD_NT)
+  for (int t = tid; t < L; t += DEC_NT)
     s[t] = id32(t < pl ? p.prompt[b * p.prompt_ld + t] : p.emitted[b * p.emitted_ld + t - pl]);
   int at = -1;  // where the continuation starts: i + g of the winning match
   for (int g = p.ngram; g >= 1 && live; --g) {  // (block-uniform conditions)
@@ -141,7 +101,7 @@ __global__ __launch_bounds__(SPD_NT) void ngram_draft_kernel(DraftP p) {
     __syncthreads();
     if (g > L - 1) continue;
     int mine = -1;
-    for (int i = tid; i + g <= L - 1; i += SPD_NT) {
+    for (int i = tid; i + g <= L - 1; i += DEC_NT) {
       bool eq = true;
       for (int c = 0; c < g; ++c) eq = eq && s[i + c] == s[L - g + c];
       if (eq) mine = i;  // i grows: the thread keeps its largest
@@ -244,7 +204,7 @@ extern "C" int gvl_attn_decode_multi(const void* qkv, void* cache, int64_t cache
   MultiP p{static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(cache), static_cast<bf16_t*>(o),
            kv_len, cache_sb, o_ld, Tmax, H * 64, (int)Q, scale};
   hipLaunchKernelGGL(attn_decode_multi_kernel, dim3((unsigned)H, (unsigned)B, (unsigned)Q),
-                     dim3(SPD_NT), 0, gvl::as_stream(stream), p);
+                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_attn_decode_multi");
   return 0;
 }
@@ -261,8 +221,8 @@ extern "C" int gvl_ngram_draft(const int64_t* prompt, int64_t prompt_ld, int64_t
   GVL_REQUIRE(n_new >= 1 && emitted_ld >= n_new && (!given || given_ld >= n_new),
               "gvl_ngram_draft: n_new=%lld, emitted_ld=%lld, given_ld=%lld", (long long)n_new,
               (long long)emitted_ld, (long long)given_ld);
-  GVL_REQUIRE(P + n_new <= SPD_MAXT, "gvl_ngram_draft: P + n_new = %lld exceeds %d",
-              (long long)(P + n_new), SPD_MAXT);
+  GVL_REQUIRE(P + n_new <= DEC_MAXT, "gvl_ngram_draft: P + n_new = %lld exceeds %d",
+              (long long)(P + n_new), DEC_MAXT);
   GVL_REQUIRE(ngram >= 1 && ngram <= 4, "gvl_ngram_draft: ngram=%d out of range (1..4)", ngram);
   GVL_REQUIRE(D >= 1 && D <= SPD_MAXQ - 1, "gvl_ngram_draft: D=%d out of range (1..%d)", D,
               SPD_MAXQ - 1);
@@ -270,7 +230,7 @@ extern "C" int gvl_ngram_draft(const int64_t* prompt, int64_t prompt_ld, int64_t
   if (B == 0) return 0;
   DraftP p{prompt, plen, emitted, n, given, draft, prompt_ld, emitted_ld, given ? given_ld : 0,
            (int)P, (int)n_new, ngram, D};
-  hipLaunchKernelGGL(ngram_draft_kernel, dim3((unsigned)B), dim3(SPD_NT), 0,
+  hipLaunchKernelGGL(ngram_draft_kernel, dim3((unsigned)B), dim3(DEC_NT), 0,
                      gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_ngram_draft");
   return 0;

@@ -446,43 +446,58 @@ def attn_bwd(dout, q, k, v, o, lse, H, causal, dq, dk, dv, scale=None, drop_p=0.
     _lib.check(_L().gvl_attn_bwd(C.byref(d), C.byref(g), _stream()), "gvl_attn_bwd")
 
 
+_DECODE_SCALE = 1.0 / math.sqrt(64)
+
+
+def _attn_decode_cached(name, q, k, v, H, src, gap, out, scale):
+    """The checks, the allocation, the default scale and the call that attn_decode,
+    attn_decode_beam and attn_decode_ragged share; name is the entry point of include/gvl.h,
+    src its table or None, gap its (gap_lo, gap_hi) or None."""
+    _dev(q, k, v, src, gap[0] if gap else None)
+    R, Tk = q.shape[0], k.shape[1]
+    tail = ()
+    if gap is not None:
+        gap_lo, gap_hi = gap[0], int(gap[1])
+        if (gap_lo.dtype != torch.int32 or gap_lo.dim() != 1 or gap_lo.numel() != R or
+                not gap_lo.is_contiguous()):
+            raise ValueError("gvl: gap_lo must be a contiguous int32 [rows of q] vector")
+        if not 0 <= gap_hi <= Tk:
+            raise ValueError(f"gvl: gap_hi = {gap_hi} outside 0..Tk = {Tk}")
+        tail = (gap_lo.data_ptr(), gap_hi)
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R:
+            raise ValueError("gvl: src must be an int32 [rows of q, >= Tk] table")
+        if k.shape[0] > R or v.shape[0] > R:
+            raise ValueError("gvl: the cache has more rows than q; src could not name them")
+    elif gap is None:
+        R = k.shape[0]  # attn_decode: one sequence per cache row
+    elif k.shape[0] != R or v.shape[0] != R:
+        raise ValueError("gvl: without src the cache must have one row per row of q")
+    if name != "gvl_attn_decode":
+        tail = (_p(src), 0 if src is None else src.stride(0)) + tail
+    if out is None:
+        out = torch.empty(R, H * 64, dtype=BF16, device=q.device)
+    if scale is None:
+        scale = _DECODE_SCALE
+    _lib.check(getattr(_L(), name)(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
+                                   k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
+                                   out.data_ptr(), out.stride(0), R, H, Tk, float(scale), *tail,
+                                   _stream()), name)
+    return out
+
+
 def attn_decode(q, k, v, H, out=None, scale=None):
     """One new query per sequence over a KV cache: q [B, *] (head h at cols h*64..), k/v
     [B, Tk, *] strided views (e.g. slices of a packed [B, Tmax, 3C] cache).  -> o [B, H*64]."""
-    _dev(q, k, v)
-    B, Tk = k.shape[0], k.shape[1]
-    if out is None:
-        out = torch.empty(B, H * 64, dtype=BF16, device=q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(64)
-    _lib.check(_L().gvl_attn_decode(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
-                                    k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
-                                    out.data_ptr(), out.stride(0), B, H, Tk, float(scale),
-                                    _stream()), "gvl_attn_decode")
-    return out
+    return _attn_decode_cached("gvl_attn_decode", q, k, v, H, None, None, out, scale)
 
 
 def attn_decode_beam(q, k, v, H, src, out=None, scale=None):
     """attn_decode with cache indirection (include/gvl.h gvl_attn_decode_beam): sequence r
     reads position t from cache row src[r, t].  q [R, *]; k/v [rows, Tk, *] strided views of the
     physical cache; src int32 [R, >= Tk] with entries in [0, R).  -> o [R, H*64]."""
-    _dev(q, k, v, src)
-    _rowmajor(src, "src")
-    if src.dtype != torch.int32 or src.shape[0] != q.shape[0]:
-        raise ValueError("gvl: src must be an int32 [rows of q, >= Tk] table")
-    R, Tk = q.shape[0], k.shape[1]
-    if k.shape[0] > R or v.shape[0] > R:
-        raise ValueError("gvl: the cache has more rows than q; src could not name them")
-    if out is None:
-        out = torch.empty(R, H * 64, dtype=BF16, device=q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(64)
-    _lib.check(_L().gvl_attn_decode_beam(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
-                                         k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
-                                         out.data_ptr(), out.stride(0), R, H, Tk, float(scale),
-                                         src.data_ptr(), src.stride(0), _stream()),
-               "gvl_attn_decode_beam")
-    return out
+    return _attn_decode_cached("gvl_attn_decode_beam", q, k, v, H, src, None, out, scale)
 
 
 def attn_decode_ragged(q, k, v, H, gap_lo, gap_hi, src=None, out=None, scale=None):
@@ -490,33 +505,8 @@ def attn_decode_ragged(q, k, v, H, gap_lo, gap_hi, src=None, out=None, scale=Non
     [gap_lo[r], gap_hi) of sequence r (include/gvl.h gvl_attn_decode_ragged): the pad columns
     of a batch of right-padded prompts in a time-aligned cache.  gap_lo int32 [rows of q] on the
     device; 0 <= gap_hi <= Tk.  -> o [rows of q, H*64]."""
-    _dev(q, k, v, gap_lo, src)
-    R, Tk = q.shape[0], k.shape[1]
-    if (gap_lo.dtype != torch.int32 or gap_lo.dim() != 1 or gap_lo.numel() != R or
-            not gap_lo.is_contiguous()):
-        raise ValueError("gvl: gap_lo must be a contiguous int32 [rows of q] vector")
-    gap_hi = int(gap_hi)
-    if not 0 <= gap_hi <= Tk:
-        raise ValueError(f"gvl: gap_hi = {gap_hi} outside 0..Tk = {Tk}")
-    if src is not None:
-        _rowmajor(src, "src")
-        if src.dtype != torch.int32 or src.shape[0] != R:
-            raise ValueError("gvl: src must be an int32 [rows of q, >= Tk] table")
-        if k.shape[0] > R or v.shape[0] > R:
-            raise ValueError("gvl: the cache has more rows than q; src could not name them")
-    elif k.shape[0] != R or v.shape[0] != R:
-        raise ValueError("gvl: without src the cache must have one row per row of q")
-    if out is None:
-        out = torch.empty(R, H * 64, dtype=BF16, device=q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(64)
-    _lib.check(_L().gvl_attn_decode_ragged(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0),
-                                           k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
-                                           out.data_ptr(), out.stride(0), R, H, Tk, float(scale),
-                                           _p(src), 0 if src is None else src.stride(0),
-                                           gap_lo.data_ptr(), gap_hi, _stream()),
-               "gvl_attn_decode_ragged")
-    return out
+    return _attn_decode_cached("gvl_attn_decode_ragged", q, k, v, H, src, (gap_lo, gap_hi), out,
+                               scale)
 
 
 def _i32_vec(t, rows, name):
@@ -551,7 +541,7 @@ def attn_decode_multi(qkv, cache, kv_len, H, out=None, scale=None):
     elif out.dtype != BF16 or out.shape != (B * Q, C) or out.stride(1) != 1:
         raise ValueError("gvl: attn_decode_multi writes a bf16 [B*Q, C] row-major tensor")
     if scale is None:
-        scale = 1.0 / math.sqrt(64)
+        scale = _DECODE_SCALE
     _lib.check(_L().gvl_attn_decode_multi(qkv.data_ptr(), cache.data_ptr(), cache.stride(0),
                                           cache.shape[1], kv_len.data_ptr(), out.data_ptr(),
                                           out.stride(0), B, H, Q, float(scale), _stream()),

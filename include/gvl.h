@@ -361,8 +361,9 @@ int gvl_sample(const void* logits, int64_t ld, int32_t logits_fp32, int64_t rows
  * clamps an entry outside that range so a bad table cannot read outside the cache): its key is
  * at k + row*k_sb + t*k_st + h*64, likewise v.  q and o are indexed by r as before.  Same
  * limits (Tk <= 4096, 16-byte-aligned rows), arithmetic and accumulation order as
- * gvl_attn_decode: on a cache gathered by src the two give the same bits.  A beam step only
- * rewrites the small src table instead of copying reordered cache rows.
+ * gvl_attn_decode: on a cache gathered by src the two give the same bits (both are the one
+ * function body attn_decode_body, csrc/attn_decode.h; only the address of a key differs).  A
+ * beam step only rewrites the small src table instead of copying reordered cache rows.
  *
  * gvl_beam_step: one beam-search step for B items x K beams (1 <= K <= 8, K <= V <= 65536),
  * row r = b*K + j.  logits [B*K, V] bf16 or fp32 (row stride ld); score_in [B*K] fp32 is the
@@ -411,7 +412,8 @@ int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B
  *   A sequence with every key inside the gap (gap_lo[r] <= 0 and gap_hi == Tk) writes zeros.
  *   Every key and value outside the gap is handled by the thread, and summed in the place, it
  *   has in gvl_attn_decode: with an empty gap (gap_lo[r] == gap_hi) the output has the bits of
- *   gvl_attn_decode (src null) or gvl_attn_decode_beam (src given).
+ *   gvl_attn_decode (src null) or gvl_attn_decode_beam (src given).  (All of them are the one
+ *   function body attn_decode_body, csrc/attn_decode.h; the gap only skips loop iterations.)
  * Limits as there (Tk in 1..4096, 16-byte-aligned rows, B <= 65535; src_ld >= Tk when src is
  * given), and 0 <= gap_hi <= Tk, gap_lo non-null: checked on the host before the launch (-1 and
  * gvl_last_error naming the argument). */
@@ -435,7 +437,8 @@ int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k, int64_t k
  * qkv[b, j] into cache[b, L + j] for every j < Q.
  *   Bit property: query j's output has exactly the bits of gvl_attn_decode with Tk = L + j + 1 on
  *   a cache that holds the same values: every key keeps its thread and every value its thread
- *   group and place in the sums.
+ *   group and place in the sums.  (Both are the one function body attn_decode_body,
+ *   csrc/attn_decode.h; only the address of a key or value differs.)
  *   Nothing in the launch reads the cache at or past L, so the append races with no load and no
  *   separate scatter is needed.  Cache columns from L + Q on, the q columns of the cache and,
  *   for query j, the qkv rows of later queries are never loaded: a NaN there reaches no output

@@ -41,6 +41,22 @@ def test_attn_decode_matches_reference(cuda):
         assert err < 1e-2
 
 
+def test_attn_decode_rejects_more_rows_than_the_grid_holds(cuda):
+    # B is gridDim.y (<= 65535): the host check names it, and nothing is launched
+    import gvl.kernels as K
+    from gvl._lib import GvlError
+    B = 65536
+    q = torch.zeros(B, 64, dtype=BF, device=cuda)
+    kv = torch.zeros(B, 1, 128, dtype=BF, device=cuda)
+    out = torch.full((B, 64), 7.0, dtype=BF, device=cuda)
+    with pytest.raises(GvlError, match="gvl_attn_decode: B=65536"):
+        K.attn_decode(q, kv[:, :, :64], kv[:, :, 64:], 1, out=out)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
+    K.attn_decode(q[:-1], kv[:-1, :, :64], kv[:-1, :, 64:], 1, out=out[:-1])  # 65535 rows run
+    assert (out[:-1] == 0).all() and out[-1, 0] == 7.0
+
+
 @pytest.mark.parametrize("temperature,top_k,top_p", [(1.0, 0, 1.0), (1.0, 50, 1.0), (0.8, 0, 0.9),
                                                      (1.3, 0, 0.5), (0.7, 20, 0.8)])
 def test_sampler_matches_reference_distribution(cuda, temperature, top_k, top_p):
