@@ -18,7 +18,8 @@ import pytest
 import torch
 
 from tests import rowwise_ref as R
-from tests.helpers import assert_bf16_close, assert_f32_close, f64, margins_out, rel_err_rows
+from tests.helpers import (F32_UNIT, assert_bf16_close, assert_f32_close, f64, margins_out,
+                           ulp_bf16)
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -50,6 +51,13 @@ def _arena(t, cuda):
         return bool(torch.all(big[:off] == SENT)) and bool(torch.all(big[off + n:] == SENT))
 
     return big[off:off + n], untouched
+
+
+def _bound_used(got, ref64, scale, slack):
+    """The worst |got - ref| as a fraction of assert_bf16_close's bound (what the margins file
+    keeps next to the error in ulps, which says little where the reference cancels to ~0)."""
+    tol = ulp_bf16(ref64) + slack * F32_UNIT * np.abs(f64(scale))
+    return float((np.abs(f64(got) - f64(ref64)) / tol).max()) if np.size(ref64) else 0.0
 
 
 def _bits(t):
@@ -184,15 +192,15 @@ def test_grad_norm_grid_stride_and_tail(cuda, n):
 
 
 # -------------------------------------------------------------------------- LayerNorm
-def _ln_slacks():
-    base = R.ln_baseline()
+def _ln_slacks(base=None):
+    base = base or R.ln_baseline()
     # y = (x - mean) * rstd * w + b: the errors of mean and rstd, then a subtraction, two
     # products and a sum (one fp32 rounding each)
     return base, 4 * base["mean"], 4 * base["rstd"], 4 * (base["mean"] + base["rstd"]) + 4
 
 
-def _ln_check_fwd(x, w, b, y, mean, rstd, name):
-    base, sm, sr, sy = _ln_slacks()
+def _ln_check_fwd(x, w, b, y, mean, rstd, name, base=None):
+    base, sm, sr, sy = _ln_slacks(base)
     ref = R.ln_ref64(x, w, b)
     em = assert_f32_close(mean.cpu(), ref["mean"], ref["scale_mean"], sm, name=name + " mean")
     er = assert_f32_close(rstd.cpu(), ref["rstd"], ref["scale_rstd"], sr, name=name + " rstd")
@@ -206,11 +214,11 @@ def test_layernorm_per_row(cuda, rows, C):
     """Rows scaled by 2**-6 .. 2**6 (a global max-norm sees only the largest): mean and rstd
     against float64 within 4 x the CPU fp32 baseline (two-pass torch: 0.90 units of
     2**-24 * mean|x| for the mean, 2.53 units of 2**-24 * rstd for rstd), y per element to one
-    bf16 ulp, dx (plain, and accumulated in place over the residual) below 1e-2 of every row's
-    own max.  Then x and y as column slices (ld = C + 8) of sentinel-filled buffers with
-    stats=False: the same y bit for bit, nothing outside the slice written, NaNs next to x
-    never read.  C = 8 is the minimum, 776 the first width of the IT = 4 instantiation; 9 and
-    37 rows leave half-filled forward blocks.
+    bf16 ulp, dx (plain, and accumulated in place over the residual) per element as in
+    test_layernorm_bwd_dx_every_route.  Then x and y as column slices (ld = C + 8) of
+    sentinel-filled buffers with stats=False: the same y bit for bit, nothing outside the slice
+    written, NaNs next to x never read.  C = 8 is the minimum, 776 the first width of the
+    IT = 4 instantiation; 9 and 37 rows leave half-filled forward blocks.
     Measured on the MI355X: mean at most 0.50, rstd 1.68 units, against bounds of 3.6 and 10.1."""
     K_ = _k()
     x, w, b, dy, prev = R.ln_inputs(rows, C)
@@ -222,12 +230,14 @@ def test_layernorm_per_row(cuda, rows, C):
     _record(f"layernorm:{rows}x{C}", dict(kernel_units=dict(mean=em, rstd=er),
                                           cpu_baseline_units=R.ln_baseline()))
     # backward from the kernel's own statistics (what the product feeds it)
-    want = R.ln_bwd_ref64(dy, x, w, ref["mean"], ref["rstd"])
+    slack = R.ln_bwd_slack()["dx"]
+    want, scale = R.ln_bwd_dx_ref64(dy, x, w, mean.cpu(), rstd.cpu())
     dx = K_.layernorm_bwd(dyd, xd, wd_, mean, rstd)
-    assert rel_err_rows(dx.cpu(), want) < 1e-2
+    assert_bf16_close(dx.cpu(), want, scale=scale, slack=slack, name=name + " dx")
     acc = prev.to(cuda)
     K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dx=acc, accumulate_dx=True)  # dx aliases the residual
-    assert rel_err_rows(acc.cpu(), want + f64(prev)) < 1e-2
+    wantp, scalep = R.ln_bwd_dx_ref64(dy, x, w, mean.cpu(), rstd.cpu(), prev)
+    assert_bf16_close(acc.cpu(), wantp, scale=scalep, slack=slack, name=name + " dx += ")
     # strided views, no statistics
     xbuf = torch.full((rows, C + 8), float("nan"), dtype=BF, device=cuda)
     xbuf[:, 8:] = xd
@@ -261,6 +271,285 @@ def test_layernorm_constant_and_offset_rows(cuda, C):
     want = 1.0 / math.sqrt(float(np.float32(R.LN_EPS)))
     assert abs(float(rstd[0]) - want) <= _ln_slacks()[2] * 2.0 ** -24 * want
     assert torch.equal(_bits(y[0]), _bits(b))
+
+
+@pytest.mark.parametrize("rows,C", R.LN_FWD_TALL)
+def test_layernorm_fwd_second_persistent_pass(cuda, rows, C):
+    """More than LN_FWD_MAXB * 8 = 8192 rows: the half-waves of the persistent forward take a
+    second row (8192: the last size with one pass; 8193: one half-wave alone in the second;
+    8203: a full block and a partial one).  Same bounds as test_layernorm_per_row from a CPU
+    baseline of these shapes' own (rowwise_ref.ln_fwd_tall_baseline: mean 0.98, rstd 4.14
+    units).
+    Measured on the MI355X: mean at most 0.90, rstd 3.38 units, against bounds of 3.9 and 16.6."""
+    K_ = _k()
+    x, w, b, _, _ = R.ln_inputs(rows, C)
+    y, mean, rstd = K_.layernorm_fwd(x.to(cuda), w.to(cuda), b.to(cuda), eps=R.LN_EPS)
+    base = R.ln_fwd_tall_baseline()
+    _, em, er = _ln_check_fwd(x, w, b, y, mean, rstd, f"layernorm {rows}x{C}", base=base)
+    _record(f"layernorm:tall:{rows}x{C}", dict(kernel_units=dict(mean=em, rstd=er),
+                                               cpu_baseline_units=base))
+
+
+# ----------------------------------------------------------------- LayerNorm backward
+def _ln_stats(cuda, x, w, b):
+    """The kernel's own fp32 statistics (what the product feeds the backward; exact inputs of
+    the reference) -> (x, w on the device, mean, rstd)."""
+    xd, wd_ = x.to(cuda), w.to(cuda)
+    _, mean, rstd = _k().layernorm_fwd(xd, wd_, b.to(cuda), eps=R.LN_EPS)
+    return xd, wd_, mean, rstd
+
+
+def _nan_view(t, cuda, ld, off):
+    """t as columns off .. off + C of a NaN-filled [rows, ld] buffer on the device."""
+    buf = torch.full((t.shape[0], ld), float("nan"), dtype=t.dtype, device=cuda)
+    buf[:, off:off + t.shape[1]] = t.to(cuda)
+    return buf[:, off:off + t.shape[1]]
+
+
+def _ln_bwd_dx_routes(cuda, x, w, b, dy, prev, name):
+    """dx on the three routes and the strided run -> (worst error in bf16 ulps, worst fraction
+    of the bound used)."""
+    K_ = _k()
+    rows, C = x.shape
+    slack = R.ln_bwd_slack()["dx"]
+    xd, wd_, mean, rstd = _ln_stats(cuda, x, w, b)
+    dyd = dy.to(cuda)
+    want, scale = R.ln_bwd_dx_ref64(dy, x, w, mean.cpu(), rstd.cpu())
+    wantp, scalep = want + f64(prev), scale + np.abs(f64(prev))
+    dx = torch.full((rows, C), float("nan"), dtype=BF, device=cuda)
+    K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dx=dx)
+    e1 = assert_bf16_close(dx.cpu(), want, scale=scale, slack=slack, name=name + " dx")
+    u1 = _bound_used(dx.cpu(), want, scale, slack)
+    acc = prev.to(cuda)
+    K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dx=acc, accumulate_dx=True)
+    e2 = assert_bf16_close(acc.cpu(), wantp, scale=scalep, slack=slack, name=name + " dx +=")
+    u2 = _bound_used(acc.cpu(), wantp, scalep, slack)
+    prev_d = prev.to(cuda)
+    dx2 = torch.full((rows, C), float("nan"), dtype=BF, device=cuda)
+    K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dx=dx2, residual=prev_d)
+    assert torch.equal(_bits(dx2), _bits(acc)), name + ": residual route differs from in place"
+    assert torch.equal(_bits(prev_d), _bits(prev)), name + ": the residual was written"
+    # four leading dimensions at once; NaN next to every operand, sentinels around dx
+    dbuf = torch.full((rows + 1, C + 32), SENT, dtype=BF, device=cuda)
+    K_.layernorm_bwd(_nan_view(dy, cuda, C + 8, 8), _nan_view(x, cuda, C + 16, 16), wd_, mean, rstd,
+                     dx=dbuf[:rows, 16:16 + C], residual=_nan_view(prev, cuda, C + 24, 8))
+    assert torch.equal(_bits(dbuf[:rows, 16:16 + C]), _bits(dx2)), name + ": strided run differs"
+    assert torch.all(dbuf[:, :16] == SENT) and torch.all(dbuf[:, 16 + C:] == SENT)
+    assert torch.all(dbuf[rows:] == SENT)
+    return max(e1, e2), max(u1, u2)
+
+
+@pytest.mark.parametrize("rows,C", R.LN_BWD_SHAPES)
+def test_layernorm_bwd_dx_every_route(cuda, rows, C):
+    """Every element of dx within one bf16 ulp + 4 x max(CPU baseline, 1) fp32 roundings of the
+    added terms, rstd * (|g| + mean|g| + |xh| mean|g xh|) + |prev|, of the float64 backward from
+    the kernel's own statistics: stored, accumulated in place over prev, and with prev as a
+    separate residual (the last two bit-identical, the residual's bits kept).  Then dy, x, the
+    residual and dx with four different leading dimensions, the inputs inside NaN-filled
+    buffers, dx inside sentinels: the same bits, nothing else written.  Widths 256 / 264 / 520
+    end exactly at, inside the second and inside the third 4-column chunk of a lane; 1 .. 9 rows
+    leave waves of the block idle, 129 and 136 rows are 17 blocks; 4088 / 4096 / 4099 rows are
+    511 blocks, the 512-block cap with two rows per wave, and a third pass for three waves (the
+    prefetch guard row + stride < rows).  The CPU baseline (rowwise_ref.ln_bwd_baseline, fp32
+    torch) is 4.76 units, so the slack is 19 fp32 roundings: 2**-20 of the terms, nothing unless
+    they cancel.
+    Measured on the MI355X: no element of any shape or route uses more than 0.500 of its bound
+    (correctly rounded but for near-ties).  In ulps of the reference the worst is 46.5 (136 x
+    520), at an element that cancels to almost nothing, where the slack term is the bound."""
+    x, w, b, dy, prev = R.ln_inputs(rows, C)
+    e, u = _ln_bwd_dx_routes(cuda, x, w, b, dy, prev, f"layernorm_bwd {rows}x{C}")
+    base = R.ln_bwd_baseline()["cases"][f"{rows}x{C}"]["dx"]
+    _record(f"layernorm_bwd_dx:{rows}x{C}", dict(worst_ulp=e, bound_used=u, cpu_baseline_units=base,
+                                                 slack_units=R.ln_bwd_slack()["dx"]))
+
+
+def _pair(dw, db, cuda):
+    """[pad | dw | db | pad] in one sentinel-filled device buffer; a tensor goes in as it is,
+    None leaves sentinels where it would stand -> (dw view or None, db view or None, buffer)."""
+    C = (dw if dw is not None else db).numel()
+    buf = torch.full((2 * C + 16,), SENT, dtype=BF)
+    if dw is not None:
+        buf[8:8 + C] = dw
+    if db is not None:
+        buf[8 + C:8 + 2 * C] = db
+    buf = buf.to(cuda)
+    return (buf[8:8 + C] if dw is not None else None,
+            buf[8 + C:8 + 2 * C] if db is not None else None, buf)
+
+
+def _pair_untouched(buf, C, dw, db):
+    ok = bool(torch.all(buf[:8] == SENT)) and bool(torch.all(buf[8 + 2 * C:] == SENT))
+    if dw is None:
+        ok = ok and bool(torch.all(buf[8:8 + C] == SENT))
+    if db is None:
+        ok = ok and bool(torch.all(buf[8 + C:8 + 2 * C] == SENT))
+    return ok
+
+
+def _ln_bwd_wb_variants(cuda, x, w, b, dy, name, db_prev=None):
+    """dw / db stored, accumulated, and each alone -> (dict(worst_ulp, bound_used) per
+    quantity, the stored and the accumulated db on the CPU)."""
+    K_ = _k()
+    rows, C = x.shape
+    S = R.ln_bwd_slack()
+    xd, wd_, mean, rstd = _ln_stats(cuda, x, w, b)
+    dyd = dy.to(cuda)
+    dwp, dbp = R.ln_wb_prev(C)
+    if db_prev is not None:
+        dbp = db_prev
+    ref = R.ln_bwd_wb_ref64(dy, x, mean.cpu(), rstd.cpu())
+    refp = R.ln_bwd_wb_ref64(dy, x, mean.cpu(), rstd.cpu(), dwp, dbp)
+    nan = torch.full((C,), float("nan"), dtype=BF)
+    worst, used = dict(dw=0.0, db=0.0), dict(dw=0.0, db=0.0)
+
+    def check(got, r, k, what):
+        e = assert_bf16_close(got.cpu(), r[k], scale=r["scale_" + k], slack=S[k],
+                              name=f"{name} {k} {what}")
+        worst[k] = max(worst[k], e)
+        used[k] = max(used[k], _bound_used(got.cpu(), r[k], r["scale_" + k], S[k]))
+
+    dwd, dw_ok = _arena(nan, cuda)
+    dbd, db_ok = _arena(nan, cuda)
+    K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dw=dwd, db=dbd)
+    assert dw_ok() and db_ok(), name + ": a store outside dw / db"
+    check(dwd, ref, "dw", "store"), check(dbd, ref, "db", "store")
+    dwa, dwa_ok = _arena(dwp, cuda)
+    dba, dba_ok = _arena(dbp, cuda)
+    K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dw=dwa, db=dba, accumulate_wb=True)
+    assert dwa_ok() and dba_ok(), name + ": a store outside dw / db"
+    check(dwa, refp, "dw", "+="), check(dba, refp, "db", "+=")
+    for k in ("dw", "db"):
+        vw, vb, buf = _pair(nan if k == "dw" else None, nan if k == "db" else None, cuda)
+        K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dw=vw, db=vb)
+        assert _pair_untouched(buf, C, vw, vb), f"{name}: {k} alone wrote outside {k}"
+        one, both = (vw, dwd) if k == "dw" else (vb, dbd)
+        check(one, ref, k, "alone")
+        assert torch.equal(_bits(one), _bits(both)), f"{name}: {k} alone differs"
+    return dict(worst_ulp=worst, bound_used=used), dbd.cpu(), dba.cpu()
+
+
+@pytest.mark.parametrize("rows,C", R.LN_BWD_SHAPES)
+def test_layernorm_bwd_dw_db_per_column(cuda, rows, C):
+    """Every column of dw = sum_r dy * xh and db = sum_r dy within one bf16 ulp + 4 x max(CPU
+    baseline, 1) fp32 roundings of sum_r |dy * xh| resp. sum_r |dy| (+ |prev|) of the float64
+    sums (the global max-norm of test_gpu_kernels.py accepts a dw that lost one of 4099 rows:
+    tests/test_helpers_cpu.py): stored into NaN-filled outputs between sentinels, accumulated
+    over random bf16 values (one rounding of sum + prev), and dw alone / db alone with
+    sentinels where the other would stand.  Shapes as test_layernorm_bwd_dx_every_route: 16,
+    17, 511 and 512 blocks walk the finalize's 16 partial groups (k = g + 16 j) and its cap.
+    CPU baseline (row-by-row fp32 sums): dw 3.48, db 0.77 units.
+    Measured on the MI355X: dw at most 0.79 ulp (8 x 1024), db 0.50 ulp (exact ties of a few
+    rows); no column of any shape or variant uses more than 0.500 of its bound."""
+    x, w, b, dy, _ = R.ln_inputs(rows, C)
+    rec, _, _ = _ln_bwd_wb_variants(cuda, x, w, b, dy, f"layernorm_bwd {rows}x{C}")
+    base = R.ln_bwd_baseline()["cases"][f"{rows}x{C}"]
+    _record(f"layernorm_bwd_wb:{rows}x{C}",
+            dict(**rec, cpu_baseline_units=dict(dw=base["dw"], db=base["db"]),
+                 slack_units={k: R.ln_bwd_slack()[k] for k in ("dw", "db")}))
+
+
+@pytest.mark.parametrize("rows,C", R.LN_COUNT_SHAPES)
+def test_layernorm_bwd_counts_every_row_once(cuda, rows, C):
+    """dy[r, c] = 1 where c == r % C: db[c] is the number of rows congruent to c (+ a small
+    integer previous value), below 256 and so exact in fp32 and bf16.  db bit for bit, stored
+    and accumulated: a dropped, doubled or misattributed row changes a count by one and no
+    tolerance is there to absorb it.  dx and dw of the same inputs go through the per-element
+    checks above.  4099 rows: the 512-block cap and the third pass; 137 x 264: 18 blocks (the
+    finalize's second trip over its groups) and a width that ends inside a lane's second chunk.
+    Measured on the MI355X: db exact at all three shapes; dx and dw at most 0.500 of their bound."""
+    x, w, b, dy, prev, db_prev, counts = R.ln_count_inputs(rows, C)
+    name = f"layernorm_bwd count {rows}x{C}"
+    rec, db, dba = _ln_bwd_wb_variants(cuda, x, w, b, dy, name, db_prev=db_prev)
+    assert torch.equal(_bits(db), _bits(counts.to(BF))), name + ": db is not the row count"
+    assert torch.equal(_bits(dba), _bits((counts + db_prev.float()).to(BF))), name + ": db +="
+    e, u = _ln_bwd_dx_routes(cuda, x, w, b, dy, prev, name)
+    base = R.ln_bwd_baseline()["cases"][f"count:{rows}x{C}"]
+    _record(f"layernorm_bwd_count:{rows}x{C}",
+            dict(worst_ulp=dict(dx=e, **rec["worst_ulp"]),
+                 bound_used=dict(dx=u, **rec["bound_used"]), cpu_baseline_units=base))
+
+
+_FIN_POOLS = {}
+
+
+def _fin_pool(cuda, C):
+    if C not in _FIN_POOLS:
+        _FIN_POOLS.clear()  # one width on the device at a time
+        _FIN_POOLS[C] = R.ln_fin_pool(C).to(cuda)
+    return _FIN_POOLS[C]
+
+
+@pytest.mark.parametrize("count", R.LN_FIN_COUNTS)
+@pytest.mark.parametrize("nblk", R.LN_FIN_NBLK)
+@pytest.mark.parametrize("C", R.LN_FIN_WIDTHS)
+def test_layernorm_finalize_synthetic_partials(cuda, C, nblk, count):
+    """gvl_layernorm_bwd_finalize_batched on fp32 [nblk, 2C] partials made here (columns scaled
+    by 2**(c % 9 - 4), every seventh cancelling): every dw / db column within one bf16 ulp +
+    4 x max(baseline, 1) roundings of sum |partial| + |prev| of the float64 column sum, the
+    baseline being a running fp32 sum on the CPU of the same item.  nblk 15 / 16 / 17 end a
+    trip over the 16 partial groups, 511 / 512 the last one; 0 gives 0 when storing and prev
+    when accumulating; C = 72 leaves a 16-column last block.  Items after the first walk the
+    nblk list, every fourth has no dw and every fourth no db (their places keep sentinels, as
+    does everything around the outputs); the 65th item is the wrapper's second launch.
+    Measured on the MI355X: no column uses more than 0.500 of its bound; 632 ulps of the
+    reference at one cancelling column (C = 776, 15 blocks), where the slack term is the bound."""
+    K_ = _k()
+    pool, pd = R.ln_fin_pool(C), _fin_pool(cuda, C)
+    items = R.ln_fin_items(nblk, C, count)
+    worst, used, wbase = 0.0, 0.0, 0.0
+    for acc in (False, True):
+        out = torch.full((count, 2, C + 16), SENT, dtype=BF)
+        for i, (s, n, hw, hb, pw, pb) in enumerate(items):
+            if hw:
+                out[i, 0, 8:8 + C] = pw if acc else float("nan")
+            if hb:
+                out[i, 1, 8:8 + C] = pb if acc else float("nan")
+        od = out.to(cuda)
+        # (an empty view has no data pointer: nblk = 0 still gets a real workspace)
+        K_.layernorm_finalize_batched(
+            [(pd[s:s + max(n, 1)], n, od[i, 0, 8:8 + C] if hw else None,
+              od[i, 1, 8:8 + C] if hb else None) for i, (s, n, hw, hb, _, _) in enumerate(items)],
+            C, accumulate=acc)
+        got = od.cpu()
+        assert torch.all(got[:, :, :8] == SENT) and torch.all(got[:, :, 8 + C:] == SENT)
+        for i, (s, n, hw, hb, pw, pb) in enumerate(items):
+            ref, E, base = R.ln_fin_ref(pool[s:s + n], torch.cat([pw, pb]) if acc else None)
+            slack = 4 * max(base, 1.0)
+            wbase = max(wbase, base)
+            for k, has, p in ((0, hw, pw), (1, hb, pb)):
+                o, rk, Ek = got[i, k, 8:8 + C], ref[k * C:(k + 1) * C], E[k * C:(k + 1) * C]
+                if not has:
+                    assert torch.all(o == SENT), f"item {i}: a null output was written"
+                    continue
+                e = assert_bf16_close(o, rk, scale=Ek, slack=slack,
+                                      name=f"finalize C={C} item {i} nblk={n} "
+                                           f"{'db' if k else 'dw'} acc={acc}")
+                worst = max(worst, e)
+                used = max(used, _bound_used(o, rk, Ek, slack))
+                if n == 0:
+                    assert torch.equal(_bits(o), _bits(p if acc else torch.zeros(C, dtype=BF)))
+    _record(f"layernorm_finalize:C{C}:nblk{nblk}:count{count}",
+            dict(worst_ulp=worst, bound_used=used, cpu_baseline_units=wbase))
+
+
+def test_layernorm_deferred_finalize_matches_in_place_at_the_cap(cuda):
+    """4099 x 128, 512 blocks: the partials left in the workspace and reduced by the batched
+    finalize give the bits of the in-place finalize (they share ln_fin_block), and dx does not
+    depend on the route."""
+    K_ = _k()
+    rows, C = 4099, 128
+    x, w, b, dy, _ = R.ln_inputs(rows, C)
+    xd, wd_, mean, rstd = _ln_stats(cuda, x, w, b)
+    dyd = dy.to(cuda)
+    dwp, dbp = R.ln_wb_prev(C)
+    dx1, (ws, nblk) = K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, defer_wb=True)
+    assert nblk == 512
+    dwb, dbb = dwp.to(cuda), dbp.to(cuda)
+    K_.layernorm_finalize_batched([(ws, nblk, dwb, dbb)], C, accumulate=True)
+    dwr, dbr = dwp.to(cuda), dbp.to(cuda)
+    dx2 = K_.layernorm_bwd(dyd, xd, wd_, mean, rstd, dw=dwr, db=dbr, accumulate_wb=True)
+    assert torch.equal(_bits(dwb), _bits(dwr)) and torch.equal(_bits(dbb), _bits(dbr))
+    assert torch.equal(_bits(dx1), _bits(dx2))
 
 
 # ---------------------------------------------------------------------- cross entropy

@@ -151,3 +151,100 @@ def test_layernorm_rejects_lost_row_and_one_pass_variance():
     assert_f32_close(r2, ref["rstd"], ref["scale_rstd"], 4 * base["rstd"])
     _, r1 = R.ln_f32(xs, one_pass=True)
     _rejects(assert_f32_close, r1[1:], ref["rstd"][1:], ref["scale_rstd"][1:], 4 * base["rstd"])
+
+
+# ----------------------------------------------------------------- LayerNorm backward
+def _bf(a):
+    return torch.from_numpy(np.asarray(a)).to(BF)
+
+
+def test_layernorm_bwd_f32_passes_at_every_shape():
+    """The condition that keeps the float64 reference inside its own bound on these inputs:
+    the kernel's formulas in fp32 torch (rowwise_ref.ln_bwd_f32), rounded to bf16, pass every
+    check of tests/test_gpu_rowwise.py at every shape it runs, storing and accumulating."""
+    S = R.ln_bwd_slack()
+    base = R.ln_bwd_baseline()
+    assert set(base["cases"]) >= {f"{r}x{c}" for r, c in R.LN_BWD_SHAPES}
+    assert all(4 * max(base[k], 1.0) == S[k] for k in S)
+    for key, (x, w, dy, prev) in R.ln_bwd_cases():
+        C = x.shape[1]
+        mean, rstd = R.ln_f32(x)
+        dwp, dbp = R.ln_wb_prev(C)
+        f = R.ln_bwd_f32(dy, x, w, mean, rstd)
+        fa = R.ln_bwd_f32(dy, x, w, mean, rstd, prev, dwp, dbp)
+        dx, sdx = R.ln_bwd_dx_ref64(dy, x, w, mean, rstd)
+        dxa, sdxa = R.ln_bwd_dx_ref64(dy, x, w, mean, rstd, prev)
+        assert_bf16_close(f["dx"].to(BF), dx, scale=sdx, slack=S["dx"], name=key + " dx")
+        assert_bf16_close(fa["dx"].to(BF), dxa, scale=sdxa, slack=S["dx"], name=key + " dx +=")
+        r, ra = R.ln_bwd_wb_ref64(dy, x, mean, rstd), R.ln_bwd_wb_ref64(dy, x, mean, rstd, dwp, dbp)
+        for k in ("dw", "db"):
+            assert_bf16_close(f[k].to(BF), r[k], scale=r["scale_" + k], slack=S[k],
+                              name=f"{key} {k}")
+            assert_bf16_close(fa[k].to(BF), ra[k], scale=ra["scale_" + k], slack=S[k],
+                              name=f"{key} {k} +=")
+    for rows, C in R.LN_COUNT_SHAPES:  # the counting inputs: db is exact, in any order
+        x, w, _, dy, _, db_prev, counts = R.ln_count_inputs(rows, C)
+        f = R.ln_bwd_f32(dy, x, w, *R.ln_f32(x), db_prev=db_prev)
+        assert torch.equal(f["db"], counts + db_prev.float())
+        assert torch.equal(f["db"].to(BF).float(), f["db"])
+
+
+def test_layernorm_bwd_rejects_lost_and_doubled_rows():
+    """dw / db of 4099 x 8 with the last row left out, or counted twice, rounded to bf16: the
+    per-column bound rejects both; the global max-norm of test_gpu_kernels.py accepts the dw
+    that lost a row (0.0085 < 1e-2), which is the gap the per-column tests close."""
+    rows, C = 4099, 8
+    x, w, _, dy, _ = R.ln_inputs(rows, C)
+    mean, rstd = R.ln_f32(x)
+    S = R.ln_bwd_slack()
+    ref = R.ln_bwd_wb_ref64(dy, x, mean, rstd)
+    lost = R.ln_bwd_wb_ref64(dy[:-1], x[:-1], mean[:-1], rstd[:-1])
+    last = R.ln_bwd_wb_ref64(dy[-1:], x[-1:], mean[-1:], rstd[-1:])
+    for k in ("dw", "db"):
+        assert_bf16_close(_bf(ref[k]), ref[k], scale=ref["scale_" + k], slack=S[k])
+        _rejects(assert_bf16_close, _bf(lost[k]), ref[k], scale=ref["scale_" + k], slack=S[k])
+        _rejects(assert_bf16_close, _bf(ref[k] + last[k]), ref[k], scale=ref["scale_" + k],
+                 slack=S[k])
+    assert rel_err(f64(_bf(lost["dw"])), ref["dw"]) < 1e-2
+
+
+def test_layernorm_bwd_dx_rejects_missing_mean_and_wrong_rstd():
+    """dx without its - mean(g) term, and dx with one row scaled by its neighbour's rstd (rows
+    differ by powers of two in scale): both fail the per-element bound at every shape kind."""
+    S = R.ln_bwd_slack()
+    for rows, C in ((9, 8), (37, 768), (136, 264)):
+        x, w, _, dy, _ = R.ln_inputs(rows, C)
+        mean, rstd = R.ln_f32(x)
+        dx, sdx = R.ln_bwd_dx_ref64(dy, x, w, mean, rstd)
+        assert_bf16_close(_bf(dx), dx, scale=sdx, slack=S["dx"])
+        g = f64(dy) * f64(w)
+        no_mean = dx + f64(rstd)[:, None] * g.mean(axis=1, keepdims=True)
+        _rejects(assert_bf16_close, _bf(no_mean), dx, scale=sdx, slack=S["dx"])
+        r2 = rstd.clone()
+        r2[rows - 1] = rstd[rows - 2]
+        wrong = R.ln_bwd_ref64(dy, x, w, mean, r2)
+        assert np.array_equal(wrong[:-1], dx[:-1])
+        with pytest.raises(AssertionError, match=rf"worst at \({rows - 1}, "):
+            assert_bf16_close(_bf(wrong), dx, scale=sdx, slack=S["dx"])
+
+
+@pytest.mark.parametrize("C", R.LN_FIN_WIDTHS)
+def test_layernorm_finalize_check_rejects_ignored_partials(C):
+    """A finalize that sums only the first trip over its 16 partial groups (k < 16): equal to
+    the reference up to 16 blocks, rejected from 17 on; a running fp32 sum rounded to bf16
+    passes at every block count, storing and accumulating."""
+    pool = R.ln_fin_pool(C)
+    prev = R.ln_fin_items(512, C, 1)[0]
+    prev = torch.cat([prev[4], prev[5]])
+    for n in R.LN_FIN_NBLK:
+        for p in (None, prev):
+            ref, E, base = R.ln_fin_ref(pool[:n], p)
+            slack = 4 * max(base, 1.0)
+            s32 = pool[:n].cumsum(dim=0)[-1] if n else torch.zeros(2 * C)
+            s32 = s32 if p is None else s32 + p.float()
+            assert_bf16_close(s32.to(BF), ref, scale=E, slack=slack, name=f"C={C} nblk={n}")
+            bad = R.ln_fin_ref(pool[:n], p, first=16)[0]
+            if n <= 16:
+                assert np.array_equal(bad, ref)
+            else:
+                _rejects(assert_bf16_close, _bf(bad), ref, scale=E, slack=slack)
