@@ -55,7 +55,9 @@ GVL_DEV bool cand_beats(float ka, uint32_t ia, float kb, uint32_t ib) {
   return ka > kb || (ka == kb && ia < ib);
 }
 
-__global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamP p) {
+// The bodies of both pairs of kernels: `step` comes from the launch arguments (gvl_beam_step) or
+// from device memory (gvl_beam_step_dev); p.step itself goes unused.
+GVL_DEV void beam_rows_body(const BeamP& p, int step) {
   __shared__ float red[BM_NT / 64];
   __shared__ float s_key[BM_NT / 64];
   __shared__ float s_raw[BM_NT / 64];
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamP p) {
     z += (x[j] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((x[j] - mx) * 1.4426950408889634f);
   z = block_sum<BM_NT>(z, red);
   const float lz = logf(z);
-  const float ln = p.len_norm[p.step + 1];
+  const float ln = p.len_norm[step + 1];
   // raw score of token i0 + j; NaN: not a candidate (past the row's end, or already selected)
 #pragma unroll
   for (int j = 0; j < BM_E; ++j)
@@ -146,13 +148,13 @@ __global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamP p) {
     if (tid == 0) {
       BeamCand c{bk, br, (int32_t)bi, 0};
       if (bi == BM_NONE) c = BeamCand{-INFINITY, -INFINITY, -1, 0};  // (V >= K: not reached)
-      else if ((int32_t)bi == p.eos) c.flen = p.step + 1;
+      else if ((int32_t)bi == p.eos) c.flen = step + 1;
       out[i] = c;
     }
   }
 }
 
-__global__ __launch_bounds__(MG_NT) void beam_merge_kernel(BeamP p) {
+GVL_DEV void beam_merge_body(const BeamP& p, int step) {
   __shared__ BeamCand c[BM_MAXK * BM_MAXK];
   __shared__ int par[BM_MAXK];
   __shared__ int nvalid;
@@ -189,13 +191,30 @@ __global__ __launch_bounds__(MG_NT) void beam_merge_kernel(BeamP p) {
     p.score_out[r0 + tid] = -INFINITY;
     p.flen_out[r0 + tid] = 0;
   }
-  const int64_t T = p.t0 + p.step;  // positions already in the cache
+  const int64_t T = p.t0 + step;  // positions already in the cache
   for (int64_t idx = tid; idx < (int64_t)K * T; idx += MG_NT) {
     const int i = (int)(idx / T);
     const int64_t t = idx - (int64_t)i * T;
     p.src_out[(r0 + i) * p.src_ld + t] = p.src_in[(r0 + par[i]) * p.src_ld + t];
   }
   if (tid < K) p.src_out[(r0 + tid) * p.src_ld + T] = (int32_t)(r0 + tid);
+}
+
+__global__ __launch_bounds__(BM_NT) void beam_rows_kernel(BeamP p) { beam_rows_body(p, p.step); }
+__global__ __launch_bounds__(MG_NT) void beam_merge_kernel(BeamP p) { beam_merge_body(p, p.step); }
+
+// gvl_beam_step_dev: (block-uniform) a step outside [0, max_steps) writes nothing.
+__global__ __launch_bounds__(BM_NT) void beam_rows_dev_kernel(BeamP p, const int32_t* step,
+                                                              int max_steps) {
+  const int st = *step;
+  if (st < 0 || st >= max_steps) return;
+  beam_rows_body(p, st);
+}
+__global__ __launch_bounds__(MG_NT) void beam_merge_dev_kernel(BeamP p, const int32_t* step,
+                                                               int max_steps) {
+  const int st = *step;
+  if (st < 0 || st >= max_steps) return;
+  beam_merge_body(p, st);
 }
 
 }  // namespace
@@ -205,26 +224,39 @@ extern "C" int64_t gvl_beam_step_workspace_size(int64_t B, int32_t K) {
   return B * K * K * (int64_t)sizeof(BeamCand);
 }
 
+// What both entry points require alike; `step` is the furthest step the launch can take
+// (gvl_beam_step_dev: max_steps - 1).
+static int check_beam(const char* fn, const void* logits, int64_t ld, int64_t B, int32_t K,
+                      int64_t V, const float* score_in, const int32_t* flen_in,
+                      const float* len_norm, int32_t step, int32_t eos, int64_t t0,
+                      const int32_t* src_in, int64_t src_ld, int64_t* tok_out, int32_t* parent_out,
+                      float* score_out, int32_t* flen_out, int32_t* src_out, void* workspace) {
+  GVL_REQUIRE(logits && score_in && flen_in && len_norm && src_in && tok_out && parent_out &&
+                  score_out && flen_out && src_out && workspace,
+              "%s: null buffer", fn);
+  GVL_REQUIRE(K >= 1 && K <= BM_MAXK, "%s: K=%d out of range (1..%d)", fn, (int)K, BM_MAXK);
+  GVL_REQUIRE(V >= K && V <= (int64_t)BM_NT * BM_E, "%s: V=%lld out of range (K=%d..%d)", fn,
+              (long long)V, (int)K, BM_NT * BM_E);
+  GVL_REQUIRE(ld >= V, "%s: ld=%lld < V=%lld", fn, (long long)ld, (long long)V);
+  GVL_REQUIRE(B >= 0 && B * K <= 0x7fffffff / BM_MAXK, "%s: B=%lld out of range", fn, (long long)B);
+  GVL_REQUIRE(eos >= -1 && eos < V, "%s: eos=%d outside the vocabulary", fn, (int)eos);
+  GVL_REQUIRE(step >= 0 && t0 >= 0 && t0 + step < src_ld,
+              "%s: position t0 + step = %lld outside the src table (src_ld=%lld)", fn,
+              (long long)(t0 + step), (long long)src_ld);
+  GVL_REQUIRE(src_in != src_out, "%s: src_in and src_out must be distinct tables", fn);
+  GVL_REQUIRE(gvl::aligned8(workspace), "%s: workspace must be 8-byte aligned", fn);
+  return 0;
+}
+
 extern "C" int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B,
                              int32_t K, int64_t V, const float* score_in, const int32_t* flen_in,
                              const float* len_norm, int32_t step, int32_t eos, int64_t t0,
                              const int32_t* src_in, int64_t src_ld, int64_t* tok_out,
                              int32_t* parent_out, float* score_out, int32_t* flen_out,
                              int32_t* src_out, void* workspace, gvl_stream_t stream) {
-  GVL_REQUIRE(logits && score_in && flen_in && len_norm && src_in && tok_out && parent_out &&
-                  score_out && flen_out && src_out && workspace,
-              "gvl_beam_step: null buffer");
-  GVL_REQUIRE(K >= 1 && K <= BM_MAXK, "gvl_beam_step: K=%d out of range (1..%d)", (int)K, BM_MAXK);
-  GVL_REQUIRE(V >= K && V <= (int64_t)BM_NT * BM_E,
-              "gvl_beam_step: V=%lld out of range (K=%d..%d)", (long long)V, (int)K, BM_NT * BM_E);
-  GVL_REQUIRE(ld >= V, "gvl_beam_step: ld=%lld < V=%lld", (long long)ld, (long long)V);
-  GVL_REQUIRE(B >= 0 && B * K <= 0x7fffffff / BM_MAXK, "gvl_beam_step: B=%lld out of range", (long long)B);
-  GVL_REQUIRE(eos >= -1 && eos < V, "gvl_beam_step: eos=%d outside the vocabulary", (int)eos);
-  GVL_REQUIRE(step >= 0 && t0 >= 0 && t0 + step < src_ld,
-              "gvl_beam_step: position t0 + step = %lld outside the src table (src_ld=%lld)",
-              (long long)(t0 + step), (long long)src_ld);
-  GVL_REQUIRE(src_in != src_out, "gvl_beam_step: src_in and src_out must be distinct tables");
-  GVL_REQUIRE(gvl::aligned8(workspace), "gvl_beam_step: workspace must be 8-byte aligned");
+  if (check_beam("gvl_beam_step", logits, ld, B, K, V, score_in, flen_in, len_norm, step, eos, t0,
+                 src_in, src_ld, tok_out, parent_out, score_out, flen_out, src_out, workspace))
+    return -1;
   if (B == 0) return 0;
   BeamP p{logits, ld, V, logits_fp32, K, step, eos, score_in, flen_in, len_norm,
           static_cast<BeamCand*>(workspace), t0, src_ld, src_in, tok_out, parent_out, score_out,
@@ -235,5 +267,31 @@ extern "C" int gvl_beam_step(const void* logits, int64_t ld, int32_t logits_fp32
   hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)B), dim3(MG_NT), 0, gvl::as_stream(stream),
                      p);
   GVL_LAUNCH_CHECK("gvl_beam_step");
+  return 0;
+}
+
+extern "C" int gvl_beam_step_dev(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B,
+                                 int32_t K, int64_t V, const float* score_in,
+                                 const int32_t* flen_in, const float* len_norm,
+                                 const int32_t* step, int32_t max_steps, int32_t eos, int64_t t0,
+                                 const int32_t* src_in, int64_t src_ld, int64_t* tok_out,
+                                 int32_t* parent_out, float* score_out, int32_t* flen_out,
+                                 int32_t* src_out, void* workspace, gvl_stream_t stream) {
+  GVL_REQUIRE(step != nullptr, "gvl_beam_step_dev: null step");
+  GVL_REQUIRE(max_steps >= 1, "gvl_beam_step_dev: max_steps=%d must be at least 1", (int)max_steps);
+  if (check_beam("gvl_beam_step_dev", logits, ld, B, K, V, score_in, flen_in, len_norm,
+                 max_steps - 1, eos, t0, src_in, src_ld, tok_out, parent_out, score_out, flen_out,
+                 src_out, workspace))
+    return -1;
+  if (B == 0) return 0;
+  BeamP p{logits, ld, V, logits_fp32, K, 0, eos, score_in, flen_in, len_norm,
+          static_cast<BeamCand*>(workspace), t0, src_ld, src_in, tok_out, parent_out, score_out,
+          flen_out, src_out};
+  hipLaunchKernelGGL(beam_rows_dev_kernel, dim3((unsigned)(B * K)), dim3(BM_NT), 0,
+                     gvl::as_stream(stream), p, step, (int)max_steps);
+  GVL_LAUNCH_CHECK("gvl_beam_step_dev");
+  hipLaunchKernelGGL(beam_merge_dev_kernel, dim3((unsigned)B), dim3(MG_NT), 0,
+                     gvl::as_stream(stream), p, step, (int)max_steps);
+  GVL_LAUNCH_CHECK("gvl_beam_step_dev");
   return 0;
 }

@@ -8,6 +8,8 @@
 // Its GAP instances (gvl_attn_decode_ragged, prompts of different lengths in one batch) leave
 // out the keys of a per-sequence range [gap_lo[sequence], gap_hi): those are never loaded and
 // take no part in the max, the sum or the accumulation; the other two instances are unchanged.
+// attn_decode_step_kernel (gvl_attn_decode_step, graph-replayed decoding) is the same body again
+// with the column of the step read from device memory and the new k / v appended in the launch.
 //
 // sample_kernel: one 1024-thread workgroup per row; the row (V <= 65536) sits in registers as
 // contiguous 64-element chunks.  softmax(logits / T) -> top-k by an 8-bit radix select on the
@@ -79,6 +81,71 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(
     kv.glo = min(max((int64_t)p.gap_lo[b], (int64_t)0), kv.ghi);
   }
   attn_decode_body(p.q + b * p.q_sb + h * 64, p.scale, p.Tk, kv, p.o + b * p.o_sb + h * 64);
+}
+
+// gvl_attn_decode_step: the column of this step is read on the device, so a replayed graph can
+// launch it with the same arguments every token.
+struct StepP {
+  const bf16_t* qkv;  // [R, 3C] contiguous: this step's c_attn output
+  bf16_t* cache;      // [R, Tmax, 3C], rows 3C apart, sequences cache_sb apart
+  bf16_t* o;          // [R, C], rows o_ld apart
+  const int32_t* t;   // one int32 on the device: the time-aligned column of this step
+  int64_t cache_sb, o_ld, Tmax, C;
+  float scale;
+  const int32_t* src;  // IND: physical cache row of (sequence, position < *t)
+  int64_t src_ld;
+  const int32_t* gap_lo;  // GAP
+  int64_t gap_hi;
+};
+
+// The KV policy (attn_decode.h) of sequence b at column tc: position t < tc is cache row b (IND:
+// src[b][t], clamped) as CacheKV presents it, position tc is the sequence's own row of qkv, and
+// the workgroup copies its head's k and v of that row into cache[b, tc] before the first barrier
+// (AppendKV's append, spec.hip).  skip() is CacheKV's.  Every load of the cache in the launch is
+// at a position below tc and every store at tc, so the append races with no load.
+template <bool IND, bool GAP>
+struct StepKV {
+  static constexpr bool may_be_empty = GAP;
+  bf16_t* cb;        // cache row b (IND: row 0)
+  bf16_t* own;       // cache[b, tc]
+  const bf16_t* nw;  // qkv[b]
+  int64_t tc, sb, C3, koff, voff;
+  const int32_t* srow;
+  int rmax;
+  int64_t glo, ghi;
+  GVL_DEV void prologue(int tid) const {  // append: 8 x 16 B of k, 8 x 16 B of v
+    if (tid >= 64 && tid < 80) {
+      const int c = tid - 64;
+      const int64_t off = (c < 8 ? koff : voff) + (c & 7) * 8;
+      *reinterpret_cast<uint4*>(own + off) = *reinterpret_cast<const uint4*>(nw + off);
+    }
+  }
+  GVL_DEV bool skip(int64_t t) const { return GAP && t >= glo && t < ghi; }
+  GVL_DEV const bf16_t* row(int64_t t) const {
+    if (t >= tc) return nw;
+    return cb + (IND ? (int64_t)min(max(srow[t], 0), rmax) * sb : 0) + t * C3;
+  }
+  GVL_DEV const bf16_t* key(int64_t t) const { return row(t) + koff; }
+  GVL_DEV const bf16_t* value(int64_t t) const { return row(t) + voff; }
+};
+
+template <bool IND, bool GAP>
+__global__ __launch_bounds__(DEC_NT) void attn_decode_step_kernel(StepP p) {
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int64_t tc = *p.t;
+  // (block-uniform) a column outside the cache: neither o nor the cache is written
+  if (tc < 0 || tc >= p.Tmax || tc >= DEC_MAXT) return;
+  const int64_t C3 = 3 * p.C;
+  bf16_t* mine = p.cache + b * p.cache_sb;
+  const bf16_t* nw = p.qkv + (int64_t)b * C3;
+  StepKV<IND, GAP> kv{IND ? p.cache : mine, mine + tc * C3, nw, tc, p.cache_sb, C3,
+                      p.C + h * 64, 2 * p.C + h * 64, IND ? p.src + b * p.src_ld : nullptr,
+                      (int)gridDim.y - 1, 0, 0};
+  if constexpr (GAP) {
+    kv.ghi = p.gap_hi;
+    kv.glo = min(max((int64_t)p.gap_lo[b], (int64_t)0), kv.ghi);
+  }
+  attn_decode_body(nw + h * 64, p.scale, tc + 1, kv, p.o + b * p.o_ld + h * 64);
 }
 
 constexpr int SMP_NT = 1024;
@@ -366,6 +433,44 @@ extern "C" int gvl_attn_decode_ragged(const void* q, int64_t q_sb, const void* k
             gap_lo, gap_hi};
   return src ? launch_cached<true, true>(fn, p, B, H, stream)
              : launch_cached<false, true>(fn, p, B, H, stream);
+}
+
+template <bool IND, bool GAP>
+static int launch_step(const StepP& p, int64_t R, int64_t H, gvl_stream_t stream) {
+  hipLaunchKernelGGL((attn_decode_step_kernel<IND, GAP>), dim3((unsigned)H, (unsigned)R),
+                     dim3(DEC_NT), 0, gvl::as_stream(stream), p);
+  GVL_LAUNCH_CHECK("gvl_attn_decode_step");
+  return 0;
+}
+
+extern "C" int gvl_attn_decode_step(const void* qkv, void* cache, int64_t cache_sb, int64_t Tmax,
+                                    const int32_t* t, void* o, int64_t o_ld, int64_t R, int64_t H,
+                                    float scale, const int32_t* src, int64_t src_ld,
+                                    const int32_t* gap_lo, int64_t gap_hi, gvl_stream_t stream) {
+  GVL_REQUIRE(qkv && cache && o, "gvl_attn_decode_step: null buffer");
+  GVL_REQUIRE(t, "gvl_attn_decode_step: null t");
+  GVL_REQUIRE(Tmax >= 1 && Tmax <= DEC_MAXT, "gvl_attn_decode_step: Tmax=%lld out of range (1..%d)",
+              (long long)Tmax, DEC_MAXT);
+  GVL_REQUIRE(R >= 0 && R <= 65535 && H >= 0 && H <= 65535,
+              "gvl_attn_decode_step: R=%lld / H=%lld out of range", (long long)R, (long long)H);
+  GVL_REQUIRE(cache_sb >= Tmax * 3 * H * 64 && cache_sb % 8 == 0,
+              "gvl_attn_decode_step: cache_sb=%lld is no stride of [Tmax, 3C] rows",
+              (long long)cache_sb);
+  GVL_REQUIRE(o_ld >= H * 64, "gvl_attn_decode_step: o_ld=%lld < C", (long long)o_ld);
+  GVL_REQUIRE(gvl::aligned16(qkv) && gvl::aligned16(cache),
+              "gvl_attn_decode_step: qkv and cache must be 16-byte aligned");
+  GVL_REQUIRE(!src || src_ld >= Tmax, "gvl_attn_decode_step: src_ld=%lld < Tmax=%lld",
+              (long long)src_ld, (long long)Tmax);
+  GVL_REQUIRE(!gap_lo || (gap_hi >= 0 && gap_hi <= Tmax),
+              "gvl_attn_decode_step: gap_hi=%lld outside 0..Tmax=%lld", (long long)gap_hi,
+              (long long)Tmax);
+  if (R == 0 || H == 0) return 0;
+  StepP p{static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(cache), static_cast<bf16_t*>(o), t,
+          cache_sb, o_ld, Tmax, H * 64, scale, src, src ? src_ld : 0, gap_lo, gap_lo ? gap_hi : 0};
+  if (gap_lo) return src ? launch_step<true, true>(p, R, H, stream)
+                         : launch_step<false, true>(p, R, H, stream);
+  return src ? launch_step<true, false>(p, R, H, stream)
+             : launch_step<false, false>(p, R, H, stream);
 }
 
 extern "C" int gvl_sample(const void* logits, int64_t ld, int32_t logits_fp32, int64_t rows,

@@ -54,13 +54,15 @@ GVL_DEV void ban(const LogitsP& p, int64_t row, int32_t v) {
   else reinterpret_cast<bf16_t*>(p.logits)[row * p.ld + v] = 0xFF80u;  // bf16 -inf
 }
 
-__global__ __launch_bounds__(LP_NT) void logits_process_kernel(LogitsP p) {
+// The one body of both kernels: n_hist and ban_eos come from the launch arguments
+// (logits_process_kernel) or from a step count in device memory (logits_process_dev_kernel).
+GVL_DEV void logits_process_body(const LogitsP& p, int n_hist, bool ban_eos) {
   __shared__ int32_t s[LP_MAXL];
   __shared__ uint32_t seen[LP_MAXV / 32];
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
   if (p.flen != nullptr && p.flen[row] > 0) return;  // (block-uniform) a finished beam
-  const int L = p.P + p.n_hist;
+  const int L = p.P + n_hist;
   const bool pen = p.pen != 1.f;
   const int64_t item = row / p.rows_per_item;
   for (int i = tid; i < L; i += LP_NT) {
@@ -112,11 +114,59 @@ __global__ __launch_bounds__(LP_NT) void logits_process_kernel(LogitsP p) {
       if (same) ban(p, row, s[i + n - 1]);
     }
   }
-  if (tid == 0 && p.ban_eos) ban(p, row, p.eos);
+  if (tid == 0 && ban_eos) ban(p, row, p.eos);
   for (int i = tid; i < p.n_bad; i += LP_NT) ban(p, row, p.bad[i]);
 }
 
+__global__ __launch_bounds__(LP_NT) void logits_process_kernel(LogitsP p) {
+  logits_process_body(p, p.n_hist, p.ban_eos != 0);
+}
+
+// gvl_logits_process_dev: n_hist = clamp(*step, 0, hist_cap), eos banned while *step < min_new
+// (p.n_hist and p.ban_eos go unused).
+__global__ __launch_bounds__(LP_NT) void logits_process_dev_kernel(LogitsP p, const int32_t* step,
+                                                                   int hist_cap, int min_new) {
+  const int st = *step;
+  logits_process_body(p, min(max(st, 0), hist_cap), st < min_new);
+}
+
 }  // namespace
+
+// What both entry points require alike; fn names the caller and cnt its history count (n_hist,
+// or hist_cap: the most *step can make it) in the message.
+static int check_logits(const char* fn, const char* cnt, const void* logits, int64_t ld, int64_t R,
+                        int64_t V, const int64_t* hist, int64_t hist_ld, int32_t n_hist,
+                        const int32_t* src, int64_t src_ld, int64_t t0, const int64_t* prompt,
+                        int64_t prompt_ld, int32_t P, int32_t rows_per_item, float rep_penalty,
+                        int32_t ngram, const int32_t* bad, int32_t n_bad) {
+  GVL_REQUIRE(logits != nullptr, "%s: null logits", fn);
+  GVL_REQUIRE(V >= 1 && V <= LP_MAXV, "%s: V=%lld out of range (1..%d)", fn, (long long)V, LP_MAXV);
+  GVL_REQUIRE(ld >= V, "%s: ld=%lld < V=%lld", fn, (long long)ld, (long long)V);
+  GVL_REQUIRE(R >= 0 && R <= 0x7fffffff, "%s: R=%lld out of range", fn, (long long)R);
+  GVL_REQUIRE(n_hist >= 0, "%s: %s=%d is negative", fn, cnt, (int)n_hist);
+  GVL_REQUIRE(P >= 0, "%s: P=%d is negative", fn, (int)P);
+  GVL_REQUIRE(n_bad >= 0, "%s: n_bad=%d is negative", fn, (int)n_bad);
+  GVL_REQUIRE((int64_t)P + n_hist <= LP_MAXL, "%s: L = P + %s = %lld exceeds %d", fn, cnt,
+              (long long)P + n_hist, LP_MAXL);
+  GVL_REQUIRE(ngram >= 0 && ngram <= LP_MAXN, "%s: ngram=%d out of range (0..%d)", fn, (int)ngram,
+              LP_MAXN);
+  GVL_REQUIRE(isfinite(rep_penalty) && rep_penalty > 0.f,
+              "%s: rep_penalty=%g must be finite and positive", fn, (double)rep_penalty);
+  GVL_REQUIRE(rows_per_item >= 1 && R % rows_per_item == 0,
+              "%s: rows_per_item=%d must be >= 1 and divide R=%lld", fn, (int)rows_per_item,
+              (long long)R);
+  GVL_REQUIRE(n_hist == 0 || hist != nullptr, "%s: null hist with %s=%d", fn, cnt, (int)n_hist);
+  GVL_REQUIRE(n_hist == 0 || hist_ld >= R, "%s: hist_ld=%lld < R=%lld", fn, (long long)hist_ld,
+              (long long)R);
+  GVL_REQUIRE(src == nullptr || (t0 >= 0 && src_ld >= t0 + n_hist),
+              "%s: src_ld=%lld does not hold t0 + %s = %lld columns (t0=%lld)", fn,
+              (long long)src_ld, cnt, (long long)(t0 + n_hist), (long long)t0);
+  GVL_REQUIRE(P == 0 || prompt != nullptr, "%s: null prompt with P=%d", fn, (int)P);
+  GVL_REQUIRE(P == 0 || prompt_ld >= P, "%s: prompt_ld=%lld < P=%d", fn, (long long)prompt_ld,
+              (int)P);
+  GVL_REQUIRE(n_bad == 0 || bad != nullptr, "%s: null bad with n_bad=%d", fn, (int)n_bad);
+  return 0;
+}
 
 extern "C" int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32, int64_t R,
                                   int64_t V, const int64_t* hist, int64_t hist_ld, int32_t n_hist,
@@ -125,37 +175,9 @@ extern "C" int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32,
                                   int32_t rows_per_item, float rep_penalty, int32_t ngram,
                                   int32_t eos, int32_t ban_eos, const int32_t* bad, int32_t n_bad,
                                   const int32_t* flen, gvl_stream_t stream) {
-  GVL_REQUIRE(logits != nullptr, "gvl_logits_process: null logits");
-  GVL_REQUIRE(V >= 1 && V <= LP_MAXV, "gvl_logits_process: V=%lld out of range (1..%d)",
-              (long long)V, LP_MAXV);
-  GVL_REQUIRE(ld >= V, "gvl_logits_process: ld=%lld < V=%lld", (long long)ld, (long long)V);
-  GVL_REQUIRE(R >= 0 && R <= 0x7fffffff, "gvl_logits_process: R=%lld out of range", (long long)R);
-  GVL_REQUIRE(n_hist >= 0, "gvl_logits_process: n_hist=%d is negative", (int)n_hist);
-  GVL_REQUIRE(P >= 0, "gvl_logits_process: P=%d is negative", (int)P);
-  GVL_REQUIRE(n_bad >= 0, "gvl_logits_process: n_bad=%d is negative", (int)n_bad);
-  GVL_REQUIRE((int64_t)P + n_hist <= LP_MAXL,
-              "gvl_logits_process: L = P + n_hist = %lld exceeds %d", (long long)P + n_hist,
-              LP_MAXL);
-  GVL_REQUIRE(ngram >= 0 && ngram <= LP_MAXN, "gvl_logits_process: ngram=%d out of range (0..%d)",
-              (int)ngram, LP_MAXN);
-  GVL_REQUIRE(isfinite(rep_penalty) && rep_penalty > 0.f,
-              "gvl_logits_process: rep_penalty=%g must be finite and positive",
-              (double)rep_penalty);
-  GVL_REQUIRE(rows_per_item >= 1 && R % rows_per_item == 0,
-              "gvl_logits_process: rows_per_item=%d must be >= 1 and divide R=%lld",
-              (int)rows_per_item, (long long)R);
-  GVL_REQUIRE(n_hist == 0 || hist != nullptr, "gvl_logits_process: null hist with n_hist=%d",
-              (int)n_hist);
-  GVL_REQUIRE(n_hist == 0 || hist_ld >= R, "gvl_logits_process: hist_ld=%lld < R=%lld",
-              (long long)hist_ld, (long long)R);
-  GVL_REQUIRE(src == nullptr || (t0 >= 0 && src_ld >= t0 + n_hist),
-              "gvl_logits_process: src_ld=%lld does not hold t0 + n_hist = %lld columns (t0=%lld)",
-              (long long)src_ld, (long long)(t0 + n_hist), (long long)t0);
-  GVL_REQUIRE(P == 0 || prompt != nullptr, "gvl_logits_process: null prompt with P=%d", (int)P);
-  GVL_REQUIRE(P == 0 || prompt_ld >= P, "gvl_logits_process: prompt_ld=%lld < P=%d",
-              (long long)prompt_ld, (int)P);
-  GVL_REQUIRE(n_bad == 0 || bad != nullptr, "gvl_logits_process: null bad with n_bad=%d",
-              (int)n_bad);
+  if (check_logits("gvl_logits_process", "n_hist", logits, ld, R, V, hist, hist_ld, n_hist, src,
+                   src_ld, t0, prompt, prompt_ld, P, rows_per_item, rep_penalty, ngram, bad, n_bad))
+    return -1;
   if (R == 0) return 0;
   if (rep_penalty == 1.f && ngram == 0 && !ban_eos && n_bad == 0) return 0;  // every control off
   LogitsP p{logits, ld, R, V, logits_fp32, hist, hist_ld, n_hist, src, src_ld, t0, prompt,
@@ -163,5 +185,28 @@ extern "C" int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32,
   hipLaunchKernelGGL(logits_process_kernel, dim3((unsigned)R), dim3(LP_NT), 0,
                      gvl::as_stream(stream), p);
   GVL_LAUNCH_CHECK("gvl_logits_process");
+  return 0;
+}
+
+extern "C" int gvl_logits_process_dev(void* logits, int64_t ld, int32_t logits_fp32, int64_t R,
+                                      int64_t V, const int64_t* hist, int64_t hist_ld,
+                                      const int32_t* step, int32_t hist_cap, const int32_t* src,
+                                      int64_t src_ld, int64_t t0, const int64_t* prompt,
+                                      int64_t prompt_ld, int32_t P, int32_t rows_per_item,
+                                      float rep_penalty, int32_t ngram, int32_t eos,
+                                      int32_t min_new, const int32_t* bad, int32_t n_bad,
+                                      const int32_t* flen, gvl_stream_t stream) {
+  GVL_REQUIRE(step != nullptr, "gvl_logits_process_dev: null step");
+  if (check_logits("gvl_logits_process_dev", "hist_cap", logits, ld, R, V, hist, hist_ld, hist_cap,
+                   src, src_ld, t0, prompt, prompt_ld, P, rows_per_item, rep_penalty, ngram, bad,
+                   n_bad))
+    return -1;
+  if (R == 0) return 0;
+  if (rep_penalty == 1.f && ngram == 0 && min_new <= 0 && n_bad == 0) return 0;  // every control off
+  LogitsP p{logits, ld, R, V, logits_fp32, hist, hist_ld, 0, src, src_ld, t0, prompt,
+            prompt_ld, P, rows_per_item, rep_penalty, ngram, eos, 0, bad, n_bad, flen};
+  hipLaunchKernelGGL(logits_process_dev_kernel, dim3((unsigned)R), dim3(LP_NT), 0,
+                     gvl::as_stream(stream), p, step, (int)hist_cap, (int)min_new);
+  GVL_LAUNCH_CHECK("gvl_logits_process_dev");
   return 0;
 }

@@ -22,7 +22,8 @@ PACKAGE_DIR = _os.path.dirname(_os.path.abspath(__file__))
 
 # KV-cached decoding (gvl.decode), resolved on first use so that `import gvl` stays light.
 # (decode.generate is not re-exported: gvl.generate is the full-recompute greedy module.)
-_DECODE_NAMES = ("beam_search", "speculative_generate", "KVDecoder", "BeamDecoder")
+_DECODE_NAMES = ("beam_search", "speculative_generate", "KVDecoder", "BeamDecoder",
+                 "GraphedGenerate", "GraphedBeamSearch")
 # Scoring of given text (gvl.score; gvl.score.score is the function behind the module's name).
 _SCORE_NAMES = ("most_likely_row", "evaluate_hellaswag", "Score")
 

@@ -135,6 +135,14 @@ SIGNATURES = {
     "gvl_logits_process": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp,
                                      c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_f32, c_i32, c_i32,
                                      c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "gvl_attn_decode_step": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                       c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "gvl_logits_process_dev": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32,
+                                         c_vp, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_f32,
+                                         c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "gvl_beam_step_dev": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp,
+                                    c_vp, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp]),
     "gvl_token_logprobs": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      c_vp, c_vp, c_vp]),
     "gvl_sequence_score": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp,

@@ -44,10 +44,20 @@ token costs one row through each block:
     kv_len, pos and the output on the device.  After start(..., prompt_lens) row r begins at
     kv_len = M + len_r, pos = len_r: its tokens overwrite its pad columns and the gap arrays go
     unused.  step(), BeamDecoder and the ragged path are as they were.
+  * graph-replayed decoding (GraphedGenerate, GraphedBeamSearch; generate / beam_search with
+    graph=True): step() issues about nine launches per block from Python, and at one row per
+    sequence the GPU finishes them faster than the host issues them.  A session keeps every
+    buffer of a token's work at a fixed address, keeps what the host used to pass per token
+    (the cache column, Tk, n_hist / ban_eos, the beam step) in device scalars read by
+    gvl_attn_decode_step, gvl_logits_process_dev and gvl_beam_step_dev, captures one token for all
+    rows as one graph and replays it.  The prefill stays eager.  Results equal the eager call's
+    bit for bit; nothing existing launches differently.
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
 from __future__ import annotations
+
+import weakref
 
 import torch
 
@@ -440,7 +450,7 @@ class _Controls:
 def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0, top_k=0,
              top_p=1.0, generator=None, return_logits=False, eos=None, return_lengths=False,
              repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-             penalize_prompt=True, prompt_lens=None):
+             penalize_prompt=True, prompt_lens=None, graph=False):
     """KV-cached decode of n_new tokens after prompt_ids [B, P].  greedy: argmax (first max);
     else temperature / top-k / top-p sampling with `generator` (a CUDA torch.Generator).
 
@@ -459,7 +469,20 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
 
     Returns the new ids [B, n_new], then if asked the per-step logits [B, steps that ran, V] as
     the decoder gave them (before the processors), then if asked lengths [B] int32: the count of
-    tokens up to and including eos, n_new for a row that never ended."""
+    tokens up to and including eos, n_new for a row that never ended.
+
+    graph: replay every token after the first as one captured graph (a GraphedGenerate built for
+    this call and closed after it: same results; its docstring says what differs for the
+    generator)."""
+    if graph:
+        with GraphedGenerate(model, prompt_ids.shape[1], n_new, greedy=greedy,
+                             temperature=temperature, top_k=top_k, top_p=top_p, eos=eos,
+                             repetition_penalty=repetition_penalty,
+                             no_repeat_ngram_size=no_repeat_ngram_size,
+                             min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
+                             penalize_prompt=penalize_prompt, return_logits=return_logits) as ses:
+            return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, generator=generator,
+                       return_lengths=return_lengths)
     B = prompt_ids.shape[0]
     dec = KVDecoder(model, B, n_new)
     lens = None
@@ -603,7 +626,8 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
 @torch.no_grad()
 def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
                 return_all=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                min_new_tokens=0, bad_tokens=None, penalize_prompt=True, prompt_lens=None):
+                min_new_tokens=0, bad_tokens=None, penalize_prompt=True, prompt_lens=None,
+                graph=False):
     """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
     hypotheses per item (prompt_lens: right-padded prompts of different lengths, as in
     generate()).  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
@@ -620,7 +644,18 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     defaults no such kernel runs.
 
     Returns (ids [B, n_new] of the best hypothesis, padded with eos past its end, lengths [B],
-    raw scores [B]); return_all: all of them in rank order, [B, K, n_new], [B, K], [B, K]."""
+    raw scores [B]); return_all: all of them in rank order, [B, K, n_new], [B, K], [B, K].
+
+    graph: replay every step after the first as one captured graph (a GraphedBeamSearch built
+    for this call and closed after it: same results)."""
+    if graph:
+        with GraphedBeamSearch(model, prompt_ids.shape[1], n_new, num_beams=num_beams, eos=eos,
+                               length_penalty=length_penalty,
+                               repetition_penalty=repetition_penalty,
+                               no_repeat_ngram_size=no_repeat_ngram_size,
+                               min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
+                               penalize_prompt=penalize_prompt) as ses:
+            return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, return_all=return_all)
     B, Kb = prompt_ids.shape[0], num_beams
     R = B * Kb
     dec = BeamDecoder(model, B, Kb, n_new)
@@ -667,3 +702,470 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     if return_all:
         return ids, lengths, scores.clone()
     return ids[:, 0], lengths[:, 0], scores[:, 0].clone()
+
+
+# ------------------------------------------------------------------ graph-replayed decoding
+def _release_graphs(graphs, state, dev):
+    """Finalizer / close() of a session: drain the device, reset the captured graphs (the
+    private memory pool goes with the last reset) and drop the static buffers."""
+    try:
+        if torch.cuda.is_initialized():
+            torch.cuda.synchronize(dev)
+    finally:
+        for g in graphs:
+            g.reset()
+        graphs.clear()
+        state.clear()
+
+
+class _Static:
+    """KVDecoder / BeamDecoder mixin for a session that replays one token's work as a graph:
+    every tensor a step touches keeps its address from call to call, and what step() takes from
+    the host each token (the cache column, the positions) is read on the device.
+
+      * the cache is allocated once with Tmax = image tokens + max_prompt + max_new; every
+        start() prefills into it (columns past a call's own are never read);
+      * what start() makes anew per call (gap_lo, pos, the cross-att model's kvz and kv_src) is
+        copied into the first call's tensors, which the captured launches name;
+      * lm_head is padded to a multiple of 8 rows once, not per token;
+      * step_dev() is step() at the column *t and the positions pos[], both on the device.
+    A session always starts with prompt_lens (all P when the caller gave none): an empty gap has
+    the bits of the instance without one, and gvl_embedding_fwd_pos those of gvl_embedding_fwd."""
+
+    _static = None
+
+    def _init_static(self, max_prompt, cap_new):
+        self.max_prompt, self.cap_new = int(max_prompt), int(cap_new)
+        self._pinned = {}
+        self.head_p = Fn.pad_vocab(self.head)[0]
+
+    def _alloc_cache(self, B, C, device):
+        self.Tmax = self.txt0 + self.max_prompt + self.cap_new
+        if self.Tmax > 4096:
+            raise ValueError(f"image tokens + max_prompt + max_new = {self.Tmax} exceeds 4096 "
+                             "cache columns")
+        if self._static is None:
+            views = super()._alloc_cache(B, C, device)
+            self._static = (views, getattr(self, "_full", None))
+        views, self._full = self._static
+        return views
+
+    def _logits(self, x2):
+        lg = K.linear(self._ln(x2, self.lnf), self.head_p)
+        V = self.head.shape[0]
+        return lg if self.head_p is self.head else lg[:, :V]
+
+    def _pin(self, name):
+        cur = getattr(self, name)
+        if cur is None:
+            return
+        first = self._pinned.setdefault(name, cur)
+        if first is not cur:
+            for dst, src in zip(*(x if isinstance(x, list) else [x] for x in (first, cur))):
+                dst.copy_(src)
+            setattr(self, name, first)
+
+    @torch.no_grad()
+    def start(self, prompt_ids, z=None, prompt_lens=None):
+        self.src = None  # (BeamDecoder: the prefill attends plain rows)
+        logits = super().start(prompt_ids, z, prompt_lens)
+        for name in ("gap_lo", "pos", "kvz", "kv_src"):
+            if hasattr(self, name):
+                self._pin(name)
+        return logits
+
+    @torch.no_grad()
+    def step_dev(self, ids, t):
+        """step(ids) with the cache column read from t (one int32 on the device) and the
+        positions from self.pos; neither is advanced here.  self.src (BeamDecoder): the table of
+        this step.  No host read and no host-side state: safe to capture."""
+        x2 = K.embedding_fwd_pos(ids, self.pos, self.wte, self.wpe)
+        for l, P in enumerate(self.blocks):
+            if self.cross is not None:
+                x2 = self._cross(l, x2, 1)
+            qkv = K.linear(self._ln(x2, P["ln1"]), *P["attn"])
+            y = K.attn_decode_step(qkv, self.cache[l], t, P["H"], src=self.src,
+                                   gap_lo=self.gap_lo, gap_hi=self.gap_hi)
+            x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
+            x2 = self._mlp(x2, P)
+        return self._logits(x2)
+
+
+class _StaticKV(_Static, KVDecoder):
+    pass
+
+
+class _StaticBeam(_Static, BeamDecoder):
+    pass
+
+
+class _GraphedSession:
+    """What GraphedGenerate and GraphedBeamSearch share: the decoder with static buffers, the
+    device counters, capture on first use, the replay loop and teardown.
+
+    Per token the host used to pass the cache column t, Tk = t + 1, n_hist / ban_eos and the
+    beam step; here they are three device scalars (t, step, and step as the int64 index torch's
+    indexing ops take) that the graph advances itself, next to the rows' positions.  Frozen at
+    capture: every address, the batch, the image-token shape, every control and sampling
+    setting, and the prefix length S = image tokens + P where a launch takes it from the host
+    (the gap end of prompts of different lengths; the beam table's t0): a call whose S needs
+    another value captures its own graph over the same buffers (stats["captures"])."""
+
+    def __init__(self, model, max_prompt, max_new, poll_every):
+        self.max_prompt, self.max_new = int(max_prompt), int(max_new)
+        self.poll_every = int(poll_every)
+        if self.max_prompt < 1 or self.max_new < 1 or self.poll_every < 1:
+            raise ValueError("max_prompt, max_new and poll_every must be at least 1")
+        self.model = model
+        self.stats = dict(captures=0, replays=0)
+        self.dec = None
+        self._key = None
+        self._graphs, self._all, self._st = {}, [], {}
+        dev = next(model.parameters()).device
+        self._finalizer = weakref.finalize(self, _release_graphs, self._all, self._st, dev)
+
+    @property
+    def closed(self) -> bool:
+        return not self._finalizer.alive
+
+    def close(self):
+        """Drain the device, reset the captured graphs and drop the buffers (idempotent).  A
+        call after close() raises."""
+        if self.closed:
+            return
+        self._finalizer()
+        self._graphs, self.dec = {}, None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _check_call(self, prompt_ids, n_new, z, prompt_lens):
+        """Everything that can refuse a call, before any launch.  -> (n_new, lens)."""
+        if self.closed:
+            raise RuntimeError(f"{type(self).__name__}.__call__ after close()")
+        if prompt_ids.dim() != 2 or prompt_ids.shape[0] < 1 or prompt_ids.shape[1] < 1:
+            raise ValueError("prompt_ids must be [B, P] with B, P >= 1")
+        B, P = prompt_ids.shape
+        n_new = self.max_new if n_new is None else int(n_new)
+        if P > self.max_prompt:
+            raise ValueError(f"a prompt of P = {P} tokens exceeds max_prompt = {self.max_prompt}")
+        if not 1 <= n_new <= self.max_new:
+            raise ValueError(f"n_new = {n_new} outside 1..max_new = {self.max_new}")
+        key = (B, None if z is None else tuple(z.shape))
+        if self._key is not None and key != self._key:
+            raise ValueError(f"batch / image-token shape {key} differs from the captured "
+                             f"{self._key}")
+        block = (self.model.gpt if hasattr(self.model, "gpt") else self.model).config.block_size
+        if prompt_lens is None:
+            if P + n_new - 1 > block:
+                raise ValueError(f"a prompt of {P} tokens + {n_new} new tokens exceeds block_size "
+                                 f"{block}")
+            lens = torch.full((B,), P, dtype=torch.int64)
+        else:
+            lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, block)
+        self._key = key
+        return n_new, lens
+
+    def _counters(self, dev):
+        st = self._st
+        st["t"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        st["step"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        st["step64"] = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _token(self):
+        """One token for all rows: the decoder pass on the tokens chosen last, then the choice."""
+        st, dec = self._st, self.dec
+        logits = dec.step_dev(st["last"], st["t"])
+        st["t"].add_(1)
+        dec.pos.add_(1)
+        self._choose(logits)
+
+    def _graph_for(self, S):
+        """The graph whose frozen prefix length serves S, captured now if there is none: a
+        warm-up token on a side stream (allocator and kernel caches warm), the state it moved
+        put back, then the capture (which runs nothing)."""
+        g = self._graphs.get(S)
+        if g is not None:
+            return g
+        dev = self._st["t"].device
+        K._gemm_workspace(dev)
+        K._gemm_tickets(dev)
+        moved = [self._st[k] for k in self.RESTORE] + [self.dec.pos]
+        saved = [v.clone() for v in moved]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._token()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        for v, s in zip(moved, saved):
+            v.copy_(s)
+        g = torch.cuda.CUDAGraph()
+        pool = self._all[0].pool() if self._all else None
+        with torch.cuda.graph(g, pool=pool):
+            self._token()
+        self._all.append(g)
+        self._graphs[S] = g
+        self.stats["captures"] += 1
+        return g
+
+    def _replay(self, g, n, done):
+        """Up to n replays; done() (a host read) is asked every poll_every of them."""
+        for i in range(1, n + 1):
+            g.replay()
+            self.stats["replays"] += 1
+            if done is not None and i < n and i % self.poll_every == 0 and done():
+                break
+
+
+class GraphedGenerate(_GraphedSession):
+    """generate() with every token after the first replayed as one captured graph.
+
+    The prefill runs eagerly into the session's static cache and the first token is chosen on
+    its logits; the graph then holds one token for all rows (embed at pos, every block with
+    gvl_attn_decode_step, ln_f, lm_head, the logits record, gvl_logits_process_dev, gvl_sample
+    on u[step], gvl_spec_accept at Q = 1 for the eos / lengths bookkeeping, the counters) and
+    the host only replays it, reading `done` once every poll_every replays when eos is given.
+    Finished rows keep emitting eos, so the extra replays change no output.  Results equal
+    generate()'s on the same inputs bit for bit.  Sampling draws the n_new uniforms of a call up
+    front (the values generate() consumes step by step): the generator ends advanced by n_new
+    draws even when eos ended the loop early.
+
+    The first call fixes the batch and the image-token shape; later calls need those,
+    P <= max_prompt and n_new <= max_new, else ValueError before any launch.  stats: captures,
+    replays.  close() (or the finalizer) resets the graph and drops the buffers."""
+
+    RESTORE = ("t", "step", "step64", "n", "lengths", "last")  # what a warm-up token moves
+
+    def __init__(self, model, max_prompt, max_new, *, greedy=False, temperature=1.0, top_k=0,
+                 top_p=1.0, eos=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_new_tokens=0, bad_tokens=None, penalize_prompt=True, return_logits=False,
+                 poll_every=8):
+        super().__init__(model, max_prompt, max_new, poll_every)
+        if greedy:
+            temperature, top_k, top_p = 1.0, 1, 1.0
+        self.greedy, self.samp = greedy, (float(temperature), int(top_k), float(top_p))
+        self.eos, self.return_logits = eos, return_logits
+        self.ctl_args = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                         bad_tokens, penalize_prompt)
+        if self.max_prompt + self.max_new > 4096:
+            raise ValueError("max_prompt + max_new exceeds 4096")
+
+    def _setup(self, B, V, dev):
+        st, cap = self._st, self.max_new
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._counters(dev)
+        st["last"] = torch.zeros(B, dtype=torch.int64, device=dev)
+        st["x"] = torch.zeros(B, dtype=torch.int64, device=dev)
+        st["n"] = torch.zeros(B, **i32)
+        st["lengths"] = torch.zeros(B, **i32)
+        st["junk"] = torch.zeros(2, B, **i32)  # gvl_spec_accept's kv_len and pos: unused here
+        st["out"] = torch.zeros(B, cap, dtype=torch.int64, device=dev)
+        st["u"] = torch.zeros(cap, B, dtype=torch.float32, device=dev)
+        st["hist"] = torch.zeros(cap, B, dtype=torch.int64, device=dev)
+        if self.return_logits:
+            st["lg"] = torch.zeros(B, cap, V, dtype=torch.float32, device=dev)
+        # the controls over a prompt buffer of max_prompt columns: a shorter prompt is moved up
+        # against the generated tokens behind entries of -1 (ragged_prompt_for_controls)
+        ctl = _Controls(torch.zeros(B, self.max_prompt, dtype=torch.int64, device=dev),
+                        *self.ctl_args)
+        self.ctl = ctl
+        self.ctl_on = ctl.always or ctl.min_new > 0
+        if ctl.prompt is not None:
+            st["prompt"] = ctl.prompt
+
+    def _choose(self, logits):
+        st, ctl = self._st, self.ctl
+        B = logits.shape[0]
+        if self.return_logits:
+            st["lg"].index_copy_(1, st["step64"], logits.to(torch.float32).unsqueeze(1))
+        if self.ctl_on:
+            K.logits_process_dev(logits, st["hist"], st["step"], self.max_new,
+                                 prompt=st.get("prompt"), repetition_penalty=ctl.pen,
+                                 no_repeat_ngram_size=ctl.ngram, eos=ctl.eos, min_new=ctl.min_new,
+                                 bad_tokens=ctl.bad)
+        u = st["u"].index_select(0, st["step64"]).view(B)
+        K.sample(logits, u, *self.samp, out=st["x"])
+        K.spec_accept(st["x"].view(B, 1), None, st["n"], st["junk"][0], st["junk"][1],
+                      st["lengths"], st["last"], st["out"], self.eos)
+        if self.ctl_on:  # the step's row of the history: eos for a row that is done, as in generate
+            st["hist"].index_copy_(0, st["step64"], st["last"].view(1, B))
+        st["step"].add_(1)
+        st["step64"].add_(1)
+
+    @torch.no_grad()
+    def __call__(self, prompt_ids, n_new=None, *, z=None, prompt_lens=None, generator=None,
+                 return_lengths=False):
+        """-> what generate() returns for these inputs and the session's settings."""
+        n_new, lens = self._check_call(prompt_ids, n_new, z, prompt_lens)
+        B, P = prompt_ids.shape
+        if self.dec is None:
+            self.dec = _StaticKV(self.model, B, n_new)
+            self.dec._init_static(self.max_prompt, self.max_new)
+        dec = self.dec
+        dec.max_new = n_new
+        logits = dec.start(prompt_ids, z, lens)
+        dev, st = logits.device, self._st
+        if not st:
+            self._setup(B, logits.shape[1], dev)
+        S = dec.t
+        # a call with every row at P tokens needs no gap: any captured gap end serves it
+        ragged = prompt_lens is not None
+        if not ragged and self._graphs and S not in self._graphs:
+            dec.gap_hi = next(iter(self._graphs))
+            dec.gap_lo.fill_(dec.gap_hi)
+        st["t"].fill_(S)
+        st["step"].zero_()
+        st["step64"].zero_()
+        st["n"].zero_()
+        st["lengths"].fill_(n_new)
+        if self.greedy:
+            st["u"].zero_()
+        else:
+            for i in range(n_new):
+                st["u"][i] = torch.rand(B, generator=generator, device=dev, dtype=torch.float32)
+        if "prompt" in st:
+            st["prompt"].fill_(-1)
+            st["prompt"][:, self.max_prompt - P:] = ragged_prompt_for_controls(prompt_ids, lens)
+        self._choose(logits)
+        if n_new > 1:
+            g = self._graph_for(dec.gap_hi)
+            done = None
+            if self.eos is not None:
+                done = lambda: bool((st["n"] >= self.max_new).all())
+            self._replay(g, n_new - 1, done)
+        out = [st["out"][:, :n_new].clone()]
+        if self.return_logits:
+            steps = n_new if self.eos is None else int(st["lengths"].max())
+            out.append(st["lg"][:, :steps].clone())
+        if return_lengths:
+            out.append(st["lengths"].clone())
+        return out[0] if len(out) == 1 else tuple(out)
+
+
+class GraphedBeamSearch(_GraphedSession):
+    """beam_search() with every step after the first replayed as one captured graph.
+
+    As GraphedGenerate, with the token choice of beam search: gvl_logits_process_dev through the
+    beam table, gvl_beam_step_dev into a second set of score / flen / table buffers, which are
+    copied back so that every launch of every step names the same addresses (the results do not
+    depend on which buffer a step wrote), and the step's tokens into the history.  With an end
+    token the host reads "every hypothesis finished" once every poll_every replays; finished
+    hypotheses only carry over, in their order, so the extra steps change no output.  The
+    table's t0 is the prefix length: a call with another P captures its own graph."""
+
+    RESTORE = ("t", "step", "step64", "score", "flen", "src", "tok")
+
+    def __init__(self, model, max_prompt, max_new, *, num_beams=4, eos=50256, length_penalty=1.0,
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
+                 penalize_prompt=True, poll_every=8):
+        super().__init__(model, max_prompt, max_new, poll_every)
+        if not 1 <= num_beams <= 8:
+            raise ValueError(f"beams={num_beams}: 1..8 supported")
+        self.Kb, self.eos, self.length_penalty = int(num_beams), eos, float(length_penalty)
+        self.ctl_args = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                         bad_tokens, penalize_prompt)
+        if self.max_prompt + self.max_new > 4096:
+            raise ValueError("max_prompt + max_new exceeds 4096")
+
+    def _setup(self, B, V, dtype, dev):
+        st, cap, Kb = self._st, self.max_new, self.Kb
+        R = B * Kb
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._counters(dev)
+        st["logits0"] = torch.empty(R, V, dtype=dtype, device=dev)
+        st["len_norm"] = torch.arange(cap + 2, dtype=torch.float32).clamp_(min=1.0).pow_(
+            -self.length_penalty).to(dev)
+        st["score"], st["score_o"] = torch.empty(R, **f32), torch.empty(R, **f32)
+        st["flen"], st["flen_o"] = torch.zeros(R, **i32), torch.zeros(R, **i32)
+        st["src"] = torch.zeros(R, self.dec.Tmax, **i32)
+        st["src_o"] = torch.zeros(R, self.dec.Tmax, **i32)
+        st["tok"] = torch.zeros(R, dtype=torch.int64, device=dev)
+        st["last"] = st["tok"]  # what the next decoder pass is fed
+        st["parent"] = torch.zeros(R, **i32)
+        nws = K._L().gvl_beam_step_workspace_size(B, Kb)
+        st["ws"] = torch.empty(max(nws, 8) // 4, **f32)
+        st["hist"] = torch.zeros(cap, R, dtype=torch.int64, device=dev)
+        ctl = _Controls(torch.zeros(B, self.max_prompt, dtype=torch.int64, device=dev),
+                        *self.ctl_args)
+        self.ctl = ctl
+        self.ctl_on = ctl.always or ctl.min_new > 0
+        if ctl.prompt is not None:
+            st["prompt"] = ctl.prompt
+
+    def _choose(self, logits):
+        st, ctl, Kb = self._st, self.ctl, self.Kb
+        R = logits.shape[0]
+        t0 = self.dec.gap_hi
+        if self.ctl_on:
+            K.logits_process_dev(logits, st["hist"], st["step"], self.max_new, src=st["src"],
+                                 t0=t0, prompt=st.get("prompt"), rows_per_item=Kb,
+                                 repetition_penalty=ctl.pen, no_repeat_ngram_size=ctl.ngram,
+                                 eos=ctl.eos, min_new=ctl.min_new, bad_tokens=ctl.bad,
+                                 flen=st["flen"])
+        K.beam_step_dev(logits, st["score"], st["flen"], st["len_norm"], st["src"], Kb, st["step"],
+                        self.max_new, self.eos, t0,
+                        (st["tok"], st["parent"], st["score_o"], st["flen_o"], st["src_o"]),
+                        st["ws"])
+        st["score"].copy_(st["score_o"])
+        st["flen"].copy_(st["flen_o"])
+        st["src"].copy_(st["src_o"])
+        st["hist"].index_copy_(0, st["step64"], st["tok"].view(1, R))
+        st["step"].add_(1)
+        st["step64"].add_(1)
+
+    @torch.no_grad()
+    def __call__(self, prompt_ids, n_new=None, *, z=None, prompt_lens=None, return_all=False):
+        """-> what beam_search() returns for these inputs and the session's settings."""
+        n_new, lens = self._check_call(prompt_ids, n_new, z, prompt_lens)
+        B, P = prompt_ids.shape
+        Kb, eos = self.Kb, self.eos
+        R = B * Kb
+        if self.dec is None:
+            self.dec = _StaticBeam(self.model, B, Kb, n_new)
+            self.dec._init_static(self.max_prompt, self.max_new)
+        dec = self.dec
+        dec.max_new = n_new
+        first = dec.start(prompt_ids, z, lens)
+        dev, st, V = first.device, self._st, first.shape[1]
+        if not st:
+            self._setup(B, V, first.dtype, dev)
+        S = t0 = dec.t
+        st["t"].fill_(S)
+        st["step"].zero_()
+        st["step64"].zero_()
+        st["logits0"].view(B, Kb, V)[:, 0] = first  # slots 1.. start empty (score -inf)
+        st["score"].fill_(float("-inf"))
+        st["score"].view(B, Kb)[:, 0] = 0.0
+        st["flen"].zero_()
+        st["src"].copy_(dec.initial_src(dev))
+        dec.src = st["src"]
+        if "prompt" in st:
+            st["prompt"].fill_(-1)
+            st["prompt"][:, self.max_prompt - P:] = ragged_prompt_for_controls(prompt_ids, lens)
+        self._choose(st["logits0"])
+        if n_new > 1:
+            g = self._graph_for(S)
+            done = None
+            if eos is not None:
+                done = lambda: bool(((st["flen"] > 0) | (st["score"] == float("-inf"))).all())
+            self._replay(g, n_new - 1, done)
+        dec.src = None
+        # beam_search()'s ending, on the steps that ran (more than it runs when the poll came
+        # late: those steps emitted eos for every hypothesis, which is its padding)
+        Sn = int(st["step"])
+        score, flen, src = st["score"], st["flen"], st["src"]
+        ids = st["hist"][:Sn].t().gather(0, src[:, t0:t0 + Sn].long())
+        if Sn < n_new:
+            ids = torch.cat([ids, ids.new_full((R, n_new - Sn), eos)], dim=1)
+        live = torch.where(score == float("-inf"), 0, Sn).to(torch.int32)
+        lengths = torch.where(flen > 0, flen, live)
+        ids, lengths, scores = ids.view(B, Kb, n_new), lengths.view(B, Kb), score.view(B, Kb)
+        if return_all:
+            return ids, lengths, scores.clone()
+        return ids[:, 0], lengths[:, 0], scores[:, 0].clone()

@@ -549,6 +549,52 @@ def attn_decode_multi(qkv, cache, kv_len, H, out=None, scale=None):
     return out
 
 
+def _dev_scalar(t, name):
+    if t.dtype != torch.int32 or t.numel() != 1:
+        raise ValueError(f"gvl: {name} must be one int32 on the device")
+
+
+def attn_decode_step(qkv, cache, t, H, src=None, gap_lo=None, gap_hi=0, out=None, scale=None):
+    """One new query per sequence with the K/V append fused and the column read on the device
+    (include/gvl.h gvl_attn_decode_step).  qkv bf16 [R, 3C] contiguous (this step's c_attn output,
+    C = H*64); cache bf16 [R, Tmax, 3C] with contiguous rows; t one int32 on the device: sequence r
+    attends positions [0, t] and its k / v land in cache[r, t].  src int32 [R, >= Tmax]: the cache
+    row of every earlier position (attn_decode_beam); gap_lo int32 [R], gap_hi: the skipped range
+    (attn_decode_ragged).  -> o [R, C]."""
+    _dev(qkv, cache, t, src, gap_lo)
+    if qkv.dim() != 2 or cache.dim() != 3:
+        raise ValueError("gvl: attn_decode_step takes qkv [R, 3C] and cache [R, Tmax, 3C]")
+    R, C3 = qkv.shape
+    C = H * 64
+    if qkv.dtype != BF16 or cache.dtype != BF16 or C3 != 3 * C or not qkv.is_contiguous():
+        raise ValueError("gvl: qkv must be a contiguous bf16 [R, 3 * H * 64] tensor")
+    if (cache.shape[0] != R or cache.shape[2] != C3 or cache.stride(2) != 1 or
+            cache.stride(1) != C3):
+        raise ValueError("gvl: cache must be [R, Tmax, 3C] with contiguous rows")
+    Tmax = cache.shape[1]
+    _dev_scalar(t, "t")
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R or src.shape[1] < Tmax:
+            raise ValueError("gvl: src must be an int32 [R, >= Tmax] table")
+    if gap_lo is not None:
+        _i32_vec(gap_lo, R, "gap_lo")
+        if not 0 <= int(gap_hi) <= Tmax:
+            raise ValueError(f"gvl: gap_hi = {gap_hi} outside 0..Tmax = {Tmax}")
+    if out is None:
+        out = torch.empty(R, C, dtype=BF16, device=qkv.device)
+    elif out.dtype != BF16 or out.shape != (R, C) or out.stride(1) != 1:
+        raise ValueError("gvl: attn_decode_step writes a bf16 [R, C] row-major tensor")
+    if scale is None:
+        scale = _DECODE_SCALE
+    _lib.check(_L().gvl_attn_decode_step(qkv.data_ptr(), cache.data_ptr(), cache.stride(0), Tmax,
+                                         t.data_ptr(), out.data_ptr(), _ld(out), R, H, float(scale),
+                                         _p(src), 0 if src is None else _ld(src), _p(gap_lo),
+                                         int(gap_hi) if gap_lo is not None else 0, _stream()),
+               "gvl_attn_decode_step")
+    return out
+
+
 def ngram_draft(prompt, plen, emitted, n, ngram, D, given=None, out=None):
     """Prompt-lookup draft (include/gvl.h gvl_ngram_draft): prompt int64 [B, P], plen int32 [B],
     emitted int64 [B, n_new] of which row b holds n[b] tokens (n int32 [B]), given optional int64
@@ -647,6 +693,101 @@ def beam_step(logits2, score, flen, len_norm, src, K, step, eos, t0, out=None, w
                                   src_o.data_ptr(), workspace.data_ptr(), _stream()),
                "gvl_beam_step")
     return out
+
+
+def beam_step_dev(logits2, score, flen, len_norm, src, K, step, max_steps, eos, t0, out,
+                  workspace):
+    """beam_step with the step count read on the device (include/gvl.h gvl_beam_step_dev): step
+    one int32 on the device, max_steps its host bound (len_norm fp32 [>= max_steps + 1], src int32
+    [B*K, >= t0 + max_steps]); a step outside [0, max_steps) writes nothing.  out and workspace
+    are the caller's (a replayed launch cannot allocate).  -> out."""
+    _dev(logits2, score, flen, len_norm, src, step, workspace, *out)
+    _rowmajor(logits2, "logits")
+    _rowmajor(src, "src")
+    R, V = logits2.shape
+    max_steps = int(max_steps)
+    if K < 1 or R % K:
+        raise ValueError(f"gvl: {R} logits rows are not B x K = {K} beams")
+    if (score.dtype != F32 or flen.dtype != torch.int32 or len_norm.dtype != F32 or
+            src.dtype != torch.int32 or logits2.dtype not in (BF16, F32)):
+        raise ValueError("gvl: beam_step_dev takes fp32 score / len_norm, int32 flen / src and "
+                         "bf16 or fp32 logits")
+    _dev_scalar(step, "step")
+    if (score.numel() != R or flen.numel() != R or src.shape[0] != R or
+            len_norm.numel() < max_steps + 1):
+        raise ValueError("gvl: beam_step_dev state does not match the logits rows / max_steps")
+    tok, parent, score_o, flen_o, src_o = out
+    if src_o.shape != src.shape or src_o.stride() != src.stride():
+        raise ValueError("gvl: the output src table must have the input table's layout")
+    if (tok.dtype != torch.int64 or parent.dtype != torch.int32 or score_o.dtype != F32 or
+            flen_o.dtype != torch.int32 or src_o.dtype != torch.int32 or
+            min(tok.numel(), parent.numel(), score_o.numel(), flen_o.numel()) < R):
+        raise ValueError("gvl: beam_step_dev writes tok int64, parent int32, score fp32, flen "
+                         "int32 [B*K] and src int32")
+    nws = _L().gvl_beam_step_workspace_size(R // K, K)
+    if workspace.numel() * workspace.element_size() < nws:
+        raise ValueError(f"gvl: beam_step workspace needs {nws} bytes")
+    _lib.check(_L().gvl_beam_step_dev(logits2.data_ptr(), logits2.stride(0),
+                                      int(logits2.dtype == F32), R // K, K, V, score.data_ptr(),
+                                      flen.data_ptr(), len_norm.data_ptr(), step.data_ptr(),
+                                      max_steps, -1 if eos is None else int(eos), int(t0),
+                                      src.data_ptr(), src.stride(0), tok.data_ptr(),
+                                      parent.data_ptr(), score_o.data_ptr(), flen_o.data_ptr(),
+                                      src_o.data_ptr(), workspace.data_ptr(), _stream()),
+               "gvl_beam_step_dev")
+    return out
+
+
+def logits_process_dev(logits2, hist, step, hist_cap, *, src=None, t0=0, prompt=None,
+                       rows_per_item=1, repetition_penalty=1.0, no_repeat_ngram_size=0, eos=None,
+                       min_new=0, bad_tokens=None, flen=None):
+    """logits_process with the step count read on the device (include/gvl.h
+    gvl_logits_process_dev): step one int32 on the device, n_hist = clamp(step, 0, hist_cap), eos
+    banned while step < min_new.  hist int64 [>= hist_cap, >= R]; src int32
+    [R, >= t0 + hist_cap]; the rest as logits_process.  -> logits2."""
+    _dev(logits2, hist, step, src, prompt, bad_tokens, flen)
+    _rowmajor(logits2, "logits")
+    R, V = logits2.shape
+    hist_cap = int(hist_cap)
+    if logits2.dtype not in (BF16, F32):
+        raise ValueError("gvl: logits_process_dev takes bf16 or fp32 logits")
+    _dev_scalar(step, "step")
+    hist_ld = 0
+    if hist_cap > 0:
+        if hist is None:
+            raise ValueError(f"gvl: logits_process_dev needs hist for hist_cap = {hist_cap}")
+        _rowmajor(hist, "hist")
+        if hist.dtype != torch.int64 or hist.shape[0] < hist_cap or hist.shape[1] < R:
+            raise ValueError("gvl: hist must be an int64 [>= hist_cap, >= rows of logits] tensor")
+        hist_ld = hist.stride(0)
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R or src.shape[1] < t0 + hist_cap:
+            raise ValueError("gvl: src must be an int32 [rows of logits, >= t0 + hist_cap] table")
+    P = 0
+    if prompt is not None:
+        _rowmajor(prompt, "prompt")
+        if (prompt.dtype != torch.int64 or rows_per_item < 1 or
+                prompt.shape[0] * rows_per_item != R):
+            raise ValueError("gvl: prompt must be an int64 [rows of logits / rows_per_item, P] "
+                             "tensor")
+        P = prompt.shape[1]
+    if bad_tokens is not None and (bad_tokens.dtype != torch.int32 or bad_tokens.dim() != 1 or
+                                   not bad_tokens.is_contiguous()):
+        raise ValueError("gvl: bad_tokens must be a contiguous int32 vector")
+    if flen is not None and (flen.dtype != torch.int32 or flen.numel() != R or
+                             not flen.is_contiguous()):
+        raise ValueError("gvl: flen must be a contiguous int32 [rows of logits] vector")
+    n_bad = 0 if bad_tokens is None else bad_tokens.numel()
+    _lib.check(_L().gvl_logits_process_dev(
+        logits2.data_ptr(), logits2.stride(0), int(logits2.dtype == F32), R, V,
+        _p(hist) if hist_cap > 0 else None, hist_ld, step.data_ptr(), hist_cap, _p(src),
+        0 if src is None else src.stride(0), int(t0), _p(prompt) if P > 0 else None,
+        0 if P == 0 else prompt.stride(0), P, int(rows_per_item), float(repetition_penalty),
+        int(no_repeat_ngram_size), -1 if eos is None else int(eos), int(min_new),
+        _p(bad_tokens) if n_bad > 0 else None, n_bad, _p(flen), _stream()),
+        "gvl_logits_process_dev")
+    return logits2
 
 
 def logits_process(logits2, hist, n_hist, *, src=None, t0=0, prompt=None, rows_per_item=1,

@@ -516,6 +516,62 @@ int gvl_logits_process(void* logits, int64_t ld, int32_t logits_fp32, int64_t R,
                        int32_t eos, int32_t ban_eos, const int32_t* bad, int32_t n_bad,
                        const int32_t* flen, gvl_stream_t stream);
 
+/* Device-stepped decoding: the entry points a decode step needs so that one token's work can be
+ * captured once as a graph and replayed (gvl.decode.GraphedGenerate / GraphedBeamSearch).  What a
+ * host-stepped launch takes as an argument that changes every token (the cache column, Tk, n_hist,
+ * ban_eos, step) is read from one int32 in device memory instead, which the graph itself
+ * advances.  Added at ABI v14 without a version bump, like the beam, logits and scoring entry
+ * points: new symbols, nothing existing changes.  Each shares its device code with the
+ * host-stepped instance, so the bit properties below hold by construction.
+ *
+ * gvl_attn_decode_step: one new query per sequence, the K/V append fused, the column read on the
+ * device.  qkv is this step's contiguous c_attn output [R, 3C] (C = H*64; q | k | v), cache the
+ * packed per-layer cache [R, Tmax, 3C] (rows 3C apart, sequences cache_sb apart, Tmax <= 4096),
+ * t one int32 on the device: the time-aligned column tc = *t of this step, o [R, C] with rows o_ld
+ * apart.  The workgroup of (sequence r, head h) copies that head's k and v of qkv[r] into
+ * cache[r, tc] and attends positions [0, tc]: position t' < tc is read from cache row r, or from
+ * row src[r*src_ld + t'] when src (int32, src_ld >= Tmax, entries clamped into [0, R)) is given;
+ * position tc is the row's own new key / value, read from qkv.  With gap_lo (int32 [R], clamped
+ * into [0, gap_hi]; 0 <= gap_hi <= Tmax) the positions [gap_lo[r], gap_hi) are left out as in
+ * gvl_attn_decode_ragged.
+ *   Bit property: o has exactly the bits of gvl_attn_decode (src and gap_lo null),
+ *   gvl_attn_decode_beam (src), or gvl_attn_decode_ragged (gap_lo, with or without src) at
+ *   Tk = tc + 1 on a cache whose column tc holds the new k / v (and, with src, src[r][tc] = r).
+ *   (All are the one function body attn_decode_body, csrc/attn_decode.h.)
+ *   Nothing in the launch loads the cache at or past column tc, the q columns of the cache or a
+ *   position inside the gap; nothing but the k and v columns of cache[:, tc] is written.
+ *   tc outside [0, Tmax) makes the launch a no-op: neither o nor the cache is written, so a
+ *   counter that ran away cannot write outside the cache.
+ *
+ * gvl_logits_process_dev: gvl_logits_process with n_hist = clamp(*step, 0, hist_cap) and the end
+ * token banned while *step < min_new; step is one int32 on the device.  hist holds at least
+ * hist_cap steps, src_ld >= t0 + hist_cap, P + hist_cap <= 4096; every other argument and every
+ * rule is gvl_logits_process's, bit for bit (one kernel body).  No launch when R == 0 or no control
+ * can ever act (p == 1, n == 0, min_new <= 0, n_bad == 0).
+ *
+ * gvl_beam_step_dev: gvl_beam_step with step = *step read on the device (one int32) and a host
+ * bound max_steps >= 1: len_norm has at least max_steps + 1 entries and src_ld >= t0 + max_steps.
+ * *step outside [0, max_steps) writes nothing; otherwise all five outputs have the bits of
+ * gvl_beam_step at that step (one pair of kernel bodies).
+ * All three check on the host what the host can see (-1 and gvl_last_error naming the argument). */
+int gvl_attn_decode_step(const void* qkv, void* cache, int64_t cache_sb, int64_t Tmax,
+                         const int32_t* t, void* o, int64_t o_ld, int64_t R, int64_t H, float scale,
+                         const int32_t* src, int64_t src_ld, const int32_t* gap_lo, int64_t gap_hi,
+                         gvl_stream_t stream);
+int gvl_logits_process_dev(void* logits, int64_t ld, int32_t logits_fp32, int64_t R, int64_t V,
+                           const int64_t* hist, int64_t hist_ld, const int32_t* step,
+                           int32_t hist_cap, const int32_t* src, int64_t src_ld, int64_t t0,
+                           const int64_t* prompt, int64_t prompt_ld, int32_t P,
+                           int32_t rows_per_item, float rep_penalty, int32_t ngram, int32_t eos,
+                           int32_t min_new, const int32_t* bad, int32_t n_bad, const int32_t* flen,
+                           gvl_stream_t stream);
+int gvl_beam_step_dev(const void* logits, int64_t ld, int32_t logits_fp32, int64_t B, int32_t K,
+                      int64_t V, const float* score_in, const int32_t* flen_in,
+                      const float* len_norm, const int32_t* step, int32_t max_steps, int32_t eos,
+                      int64_t t0, const int32_t* src_in, int64_t src_ld, int64_t* tok_out,
+                      int32_t* parent_out, float* score_out, int32_t* flen_out, int32_t* src_out,
+                      void* workspace, gvl_stream_t stream);
+
 /* Scoring of given tokens (the HellaSwag evaluation of train_gpt2.py:190-202, 394-426, caption
  * reranking, perplexity).  Added at ABI v14 without a version bump, like the beam and logits
  * entry points: new symbols, nothing existing changes.
