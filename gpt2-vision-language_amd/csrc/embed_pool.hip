@@ -90,14 +90,16 @@ __global__ __launch_bounds__(256) void emb_bwd_kernel(const int64_t* __restrict_
 // launches: every 1024-key tile is bitonic-sorted in LDS by its own block (emb_tile_kernel),
 // then each key's global rank = its index in its tile + the number of smaller keys in every
 // other tile (binary searches in LDS, emb_rank_kernel) scatters it to its sorted slot.  Then
-// one wave per sorted slot: the head of each run of equal ids sums its run and updates the
-// row.  Larger inputs run chunk after chunk (stream-ordered, so a row touched by two chunks
+// one wave per sorted slot and EMB_SLAB-column slab of the row: the head of each run of equal ids
+// sums its run and updates the row.
+// Larger inputs run chunk after chunk (stream-ordered, so a row touched by two chunks
 // is updated in chunk order).  Out-of-range ids get the reserved id field EMB_BAD_ID (still
 // unique keys: the position is kept) and are skipped.
 constexpr int EMB_CHUNK = 16384;  // 14-bit positions
 constexpr int EMB_TILE = 1024;
 constexpr uint32_t EMB_BAD_ID = 0x3FFFFu;
-constexpr int EMB_MAXC = 1024;    // 64 lanes x 8 bf16 x 2 slices
+constexpr int EMB_SLAB = 1024;    // 64 lanes x 8 bf16 x 2 slices: the columns one wave sums
+constexpr int EMB_MAXC = 2048;    // blockIdx.y picks the slab of the row (slab 0 alone at C <= 1024)
 
 __global__ __launch_bounds__(EMB_TILE / 2) void emb_tile_kernel(const int64_t* __restrict__ idx,
                                                                 int64_t base, int n, int64_t V,
@@ -166,11 +168,12 @@ __global__ __launch_bounds__(256) void emb_seg_kernel(const uint32_t* __restrict
   if (id == EMB_BAD_ID) return;
   if (i > 0 && (prev >> 14) == id) return;  // not the head of its run
   const int lane = threadIdx.x & 63;
+  const int c0 = blockIdx.y * EMB_SLAB;
   bf16_t* w = dwte + (int64_t)id * C;
   uint4 wu[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int c = lane * 8 + h * 512;
+    const int c = c0 + lane * 8 + h * 512;
     if (c < C) wu[h] = *reinterpret_cast<const uint4*>(w + c);
   }
   float acc[2][8];
@@ -185,13 +188,13 @@ __global__ __launch_bounds__(256) void emb_seg_kernel(const uint32_t* __restrict
     uint4 u[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int c = lane * 8 + h * 512;
+      const int c = c0 + lane * 8 + h * 512;
       if (c < C) u[h] = *reinterpret_cast<const uint4*>(g + c);
     }
     const uint32_t kn = j + 1 < n ? keys[j + 1] : 0xFFFFFFFFu;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int c = lane * 8 + h * 512;
+      const int c = c0 + lane * 8 + h * 512;
       if (c < C) {
         acc[h][0] += lo_bf(u[h].x); acc[h][1] += hi_bf(u[h].x); acc[h][2] += lo_bf(u[h].y);
         acc[h][3] += hi_bf(u[h].y); acc[h][4] += lo_bf(u[h].z); acc[h][5] += hi_bf(u[h].z);
@@ -204,7 +207,7 @@ __global__ __launch_bounds__(256) void emb_seg_kernel(const uint32_t* __restrict
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int c = lane * 8 + h * 512;
+    const int c = c0 + lane * 8 + h * 512;
     if (c < C) {
       const uint4 uw = wu[h];
       uint4 o;
@@ -217,13 +220,14 @@ __global__ __launch_bounds__(256) void emb_seg_kernel(const uint32_t* __restrict
   }
 }
 
-// dwpe[t] += sum over sequences g of dout[g*S + off + t], one wave per position t.
+// dwpe[t] += sum over sequences g of dout[g*S + off + t], one wave per position t and slab.
 __global__ __launch_bounds__(256) void emb_pos_kernel(const bf16_t* __restrict__ dout,
                                                        bf16_t* __restrict__ dwpe, int64_t G,
                                                        int64_t T, int C, int64_t S, int64_t off) {
   const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;
   const int lane = threadIdx.x & 63;
+  const int c0 = blockIdx.y * EMB_SLAB;
   float acc[2][8];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(256) void emb_pos_kernel(const bf16_t* __restrict__
       const bf16_t* src = dout + ((g0 + q < G ? g0 + q : g0) * S + off + t) * (int64_t)C;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int c = lane * 8 + h * 512;
+        const int c = c0 + lane * 8 + h * 512;
         u[q][h] = c < C ? *reinterpret_cast<const uint4*>(src + c) : make_uint4(0, 0, 0, 0);
       }
     }
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(256) void emb_pos_kernel(const bf16_t* __restrict__
   bf16_t* w = dwpe + t * (int64_t)C;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int c = lane * 8 + h * 512;
+    const int c = c0 + lane * 8 + h * 512;
     if (c < C) {
       const uint4 u = *reinterpret_cast<const uint4*>(w + c);
       uint4 o;
@@ -513,6 +517,7 @@ extern "C" int gvl_embedding_bwd_det(const int64_t* idx, const void* dout, void*
   GVL_REQUIRE(n_tokens % T == 0, "gvl_embedding_bwd_det: n_tokens must be a multiple of T");
   if (n_tokens == 0) return 0;
   hipStream_t s = gvl::as_stream(stream);
+  const unsigned slabs = C > EMB_SLAB ? 2 : 1;
   if (dwte) {
     GVL_REQUIRE(keys && keys_count >= gvl_embedding_bwd_workspace(n_tokens),
                 "gvl_embedding_bwd_det: key workspace too small");
@@ -524,13 +529,13 @@ extern "C" int gvl_embedding_bwd_det(const int64_t* idx, const void* dout, void*
                          tiles);
       hipLaunchKernelGGL(emb_rank_kernel, dim3(nt), dim3(EMB_TILE), nt * EMB_TILE * sizeof(uint32_t),
                          s, (const uint32_t*)tiles, nt, n, keys);
-      hipLaunchKernelGGL(emb_seg_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s,
+      hipLaunchKernelGGL(emb_seg_kernel, dim3((unsigned)((n + 3) / 4), slabs), dim3(256), 0, s,
                          (const uint32_t*)keys, n, base, static_cast<const bf16_t*>(dout),
                          static_cast<bf16_t*>(dwte), T, (int)C, out_rows_per_seq, out_offset);
     }
   }
   if (dwpe)
-    hipLaunchKernelGGL(emb_pos_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL(emb_pos_kernel, dim3((unsigned)((T + 3) / 4), slabs), dim3(256), 0, s,
                        static_cast<const bf16_t*>(dout), static_cast<bf16_t*>(dwpe), n_tokens / T,
                        T, (int)C, out_rows_per_seq, out_offset);
   GVL_LAUNCH_CHECK("gvl_embedding_bwd_det");

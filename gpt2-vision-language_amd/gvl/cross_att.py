@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import functional as Fn
 from .functional import bf
-from .gpt2 import MLP, build_optimizer, init_gpt_weights
+from .gpt2 import MLP, config_for_size, build_optimizer, init_gpt_weights
 from .gpt2 import CausalSelfAttention as CausalSelfAttention  # with the mask buffer (:19)
 from .caption import pool_clip_197_to_33_avg_with_cls
 
@@ -30,6 +30,11 @@ class GPTConfig:
     n_head: int = 12
     n_embd: int = 768
     img_embd: int = 768
+
+    @classmethod
+    def for_size(cls, name: str, **overrides) -> "GPTConfig":
+        """The config of a published size (gvl.gpt2.GPT2_SIZES), with any field overridden."""
+        return config_for_size(cls, name, **overrides)
 
 
 class CrossAttention(nn.Module):

@@ -18,6 +18,30 @@ from . import functional as Fn
 from .functional import bf
 
 
+# The published GPT-2 sizes as (n_layer, n_head, n_embd); every head is 64 wide.
+GPT2_SIZES = {
+    "gpt2": (12, 12, 768),
+    "gpt2-medium": (24, 16, 1024),
+    "gpt2-large": (36, 20, 1280),
+    "gpt2-xl": (48, 25, 1600),
+}
+MAX_N_EMBD = 2048  # the row kernels' cap (LayerNorm, deterministic embedding backward)
+
+
+def check_width(n_embd: int) -> None:
+    if n_embd > MAX_N_EMBD:
+        raise ValueError(f"n_embd={n_embd} is above the row kernels' cap of {MAX_N_EMBD} columns")
+
+
+def config_for_size(cls, name: str, **overrides):
+    if name not in GPT2_SIZES:
+        raise ValueError(f"unknown GPT-2 size {name!r}; one of {', '.join(GPT2_SIZES)}")
+    n_layer, n_head, n_embd = GPT2_SIZES[name]
+    cfg = cls(**{**dict(n_layer=n_layer, n_head=n_head, n_embd=n_embd), **overrides})
+    check_width(cfg.n_embd)
+    return cfg
+
+
 @dataclass
 class GPTConfig:
     """train_gpt2.py:76-83 (the train script overrides vocab_size to 50304)."""
@@ -27,6 +51,11 @@ class GPTConfig:
     n_head: int = 12
     n_embd: int = 768
 
+    @classmethod
+    def for_size(cls, name: str, **overrides) -> "GPTConfig":
+        """The config of a published size (GPT2_SIZES), with any field overridden."""
+        return config_for_size(cls, name, **overrides)
+
 
 class CausalSelfAttention(nn.Module):
     """train_gpt2.py:21-43: c_attn (C->3C), causal SDPA over 64-wide heads, c_proj."""
@@ -35,6 +64,7 @@ class CausalSelfAttention(nn.Module):
         super().__init__()
         if config.n_embd % config.n_head != 0 or config.n_embd // config.n_head != 64:
             raise ValueError("gvl kernels implement head_dim == 64 (n_embd / n_head)")
+        check_width(config.n_embd)
         self.c_attn = nn.Linear(config.n_embd, 3 * config.n_embd)
         self.c_proj = nn.Linear(config.n_embd, config.n_embd)
         self.c_proj.NANOGPT_SCALE_INIT = 1

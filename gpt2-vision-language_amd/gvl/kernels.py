@@ -324,6 +324,11 @@ def gemm_grouped(items, dbias=None):
 
 
 # ------------------------------------------------------------------------- LayerNorm
+# Rows of up to LN_NARROW_COLS columns run the original entry points; wider ones (GPT-2 large /
+# XL, up to 2048 columns) their *_wide forms.
+LN_NARROW_COLS = 1024
+
+
 def layernorm_fwd(x2, w, b, eps=1e-5, out=None, stats=True):
     _dev(x2)
     _rowmajor(x2, "x")
@@ -332,9 +337,10 @@ def layernorm_fwd(x2, w, b, eps=1e-5, out=None, stats=True):
         out = torch.empty(rows, cols, dtype=BF16, device=x2.device)
     mean = torch.empty(rows, dtype=F32, device=x2.device) if stats else None
     rstd = torch.empty(rows, dtype=F32, device=x2.device) if stats else None
-    _lib.check(_L().gvl_layernorm_fwd(x2.data_ptr(), x2.stride(0), w.data_ptr(), b.data_ptr(),
-                                      out.data_ptr(), out.stride(0), _p(mean), _p(rstd), rows, cols,
-                                      float(eps), _stream()), "gvl_layernorm_fwd")
+    name = "gvl_layernorm_fwd" if cols <= LN_NARROW_COLS else "gvl_layernorm_fwd_wide"
+    _lib.check(getattr(_L(), name)(x2.data_ptr(), x2.stride(0), w.data_ptr(), b.data_ptr(),
+                                   out.data_ptr(), out.stride(0), _p(mean), _p(rstd), rows, cols,
+                                   float(eps), _stream()), name)
     return out, mean, rstd
 
 
@@ -354,7 +360,14 @@ def layernorm_bwd(dy2, x2, w, mean, rstd, dx=None, accumulate_dx=False, dw=None,
     if defer_wb:
         dw = db = None
         accumulate_wb = 2
-    if residual is not None:
+    if cols > LN_NARROW_COLS:
+        _lib.check(_L().gvl_layernorm_bwd_wide(
+            dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), w.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), _p(residual),
+            residual.stride(0) if residual is not None else 0, dx.data_ptr(), dx.stride(0),
+            int(accumulate_dx or residual is not None), _p(dw), _p(db), int(accumulate_wb), _p(ws),
+            rows, cols, _stream()), "gvl_layernorm_bwd_wide")
+    elif residual is not None:
         _lib.check(_L().gvl_layernorm_bwd_res(
             dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), w.data_ptr(),
             mean.data_ptr(), rstd.data_ptr(), residual.data_ptr(), residual.stride(0),
@@ -381,9 +394,9 @@ def layernorm_finalize_batched(items, cols, accumulate=True):
         nb = (C.c_int32 * n)(*[t[1] for t in chunk])
         dw = (C.c_void_p * n)(*[_p(t[2]) for t in chunk])
         db = (C.c_void_p * n)(*[_p(t[3]) for t in chunk])
-        _lib.check(_L().gvl_layernorm_bwd_finalize_batched(ws, nb, n, int(cols), dw, db,
-                                                           int(bool(accumulate)), _stream()),
-                   "gvl_layernorm_bwd_finalize_batched")
+        name = "gvl_layernorm_bwd_finalize_batched" + ("" if cols <= LN_NARROW_COLS else "_wide")
+        _lib.check(getattr(_L(), name)(ws, nb, n, int(cols), dw, db, int(bool(accumulate)),
+                                       _stream()), name)
 
 
 # ------------------------------------------------------------------------- attention

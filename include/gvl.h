@@ -180,6 +180,28 @@ int gvl_layernorm_bwd_res(const void* dy, int64_t lddy, const void* x, int64_t l
                           const void* res, int64_t ldr, void* dx, int64_t lddx,
                           void* dw, void* db, int32_t accumulate_wb, void* workspace,
                           int64_t rows, int64_t cols, gvl_stream_t stream);
+/* Wide rows: 1024 < cols <= 2048, cols % 8 == 0 (GPT-2 large / XL, n_embd 1280 / 1600); the
+ * entry points above keep their cols <= 1024 contract and refuse these widths.  Same leading-
+ * dimension and alignment rules, same outputs, same workspace size and block count
+ * (gvl_layernorm_bwd_workspace_size / gvl_layernorm_bwd_blocks serve both).
+ * gvl_layernorm_fwd_wide: gvl_layernorm_fwd's arguments (mean / rstd optional).
+ * gvl_layernorm_bwd_wide: one entry for gvl_layernorm_bwd and gvl_layernorm_bwd_res: with
+ * accumulate_dx set, dx = res + LN'(dy), where res is a separate operand, dx itself, or null
+ * (= dx); with it clear res is not read.  accumulate_wb as above, bit 1 included.
+ * gvl_layernorm_bwd_finalize_batched_wide: gvl_layernorm_bwd_finalize_batched for the
+ * partials of gvl_layernorm_bwd_wide. */
+int gvl_layernorm_fwd_wide(const void* x, int64_t ldx, const void* w, const void* b,
+                           void* y, int64_t ldy, float* mean, float* rstd,
+                           int64_t rows, int64_t cols, float eps, gvl_stream_t stream);
+int gvl_layernorm_bwd_wide(const void* dy, int64_t lddy, const void* x, int64_t ldx,
+                           const void* w, const float* mean, const float* rstd,
+                           const void* res, int64_t ldr, void* dx, int64_t lddx,
+                           int32_t accumulate_dx, void* dw, void* db, int32_t accumulate_wb,
+                           void* workspace, int64_t rows, int64_t cols, gvl_stream_t stream);
+int gvl_layernorm_bwd_finalize_batched_wide(const float* const* ws, const int32_t* nblk,
+                                            int32_t count, int64_t cols, void* const* dw,
+                                            void* const* db, int32_t accumulate_wb,
+                                            gvl_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* Fused attention, head dim 64, bf16 in/out, fp32 online softmax.
