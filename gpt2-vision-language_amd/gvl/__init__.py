@@ -10,7 +10,9 @@ Runtime:
     beam search, speculative decoding; gvl.beam_search and gvl.speculative_generate are
     gvl.decode's), gvl.score (log-probabilities, ranks
     and multiple-choice predictions of given text; gvl.evaluate_hellaswag, gvl.most_likely_row),
-    gvl.kernels (C-ABI wrappers).
+    gvl.kernels (C-ABI wrappers), gvl.quant (int8 weight-only decoding: every gvl.decode entry
+    point takes weights="int8" or a gvl.quant.quantize_decoder(model) snapshot; the default
+    stays bf16).
 All compute goes through libgvl.so (include/gvl.h); importing a module that needs it on a
 machine without the built library raises at first use, there is no fallback.
 """

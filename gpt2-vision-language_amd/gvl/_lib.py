@@ -64,6 +64,19 @@ class AttnBwdDesc(C.Structure):
     ]
 
 
+class LinearW8Desc(C.Structure):
+    _fields_ = [
+        ("x", c_vp), ("w", c_vp), ("scale", c_vp), ("c", c_vp),
+        ("m", c_i64), ("n", c_i64), ("k", c_i64),
+        ("ldx", c_i64), ("ldw", c_i64), ("ldc", c_i64),
+        ("bias", c_vp), ("act", c_i32),
+        ("residual", c_vp), ("ldr", c_i64),
+        ("gate", c_vp),
+    ]
+
+
+LINEAR_W8_MAX_ROWS = 256  # include/gvl.h GVL_LINEAR_W8_MAX_ROWS
+
 # name -> (restype, argtypes); every symbol include/gvl.h declares.
 SIGNATURES = {
     "gvl_last_error": (C.c_char_p, []),
@@ -166,6 +179,9 @@ SIGNATURES = {
     "gvl_gate_bwd_acc_bf16": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "gvl_gate_bwd_workspace_size": (c_i64, [c_i64]),
     "gvl_f32_to_bf16": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "gvl_quantize_rows_i8": (C.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "gvl_dequantize_rows_i8": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "gvl_linear_w8": (C.c_int, [C.POINTER(LinearW8Desc), c_vp]),
 }
 
 _lib = None

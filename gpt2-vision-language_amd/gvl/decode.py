@@ -52,6 +52,12 @@ token costs one row through each block:
     gvl_attn_decode_step, gvl_logits_process_dev and gvl_beam_step_dev, captures one token for all
     rows as one graph and replays it.  The prefill stays eager.  Results equal the eager call's
     bit for bit; nothing existing launches differently.
+  * int8 weight-only decoding (weights="int8" or a gvl.quant.quantize_decoder(model) snapshot on
+    every entry point; gvl/quant.py): the block matrices and the lm_head as per-row int8.  The
+    decoders reach their linears through KVDecoder._linear: K.linear as ever by default, else
+    gvl_linear_w8 for the steps and the dequantised matrix through K.linear for the prefill.  An
+    element of gvl_linear_w8's output has the same bits at any row count, so graph replay, Q = 1
+    and speculative decoding keep their equalities in this mode too.
 
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
@@ -63,6 +69,7 @@ import torch
 
 from . import functional as Fn
 from . import kernels as K
+from . import quant
 from .functional import bf
 
 BF16 = torch.bfloat16
@@ -123,9 +130,14 @@ class KVDecoder:
     With prompt_lens (start) the prompts are right-padded rows of different lengths: see the
     module docstring."""
 
-    def __init__(self, model, batch: int, max_new: int):
+    def __init__(self, model, batch: int, max_new: int, weights=None):
         from . import caption, cross_att
         self.model = model
+        # weights: None (bf16), "int8" or a gvl.quant.quantize_decoder(model) result: the whole
+        # call then runs the quantised model (gvl.quant; _linear below)
+        self.qdec = quant.resolve_weights(model, weights)
+        self._dq = False   # prefill: dequantise each matrix ahead of its K.linear
+        self._scr = None   # the bf16 buffer it is dequantised into
         self.kind = ("caption" if isinstance(model, caption.GPT_Caption) else
                      "cross" if isinstance(model, cross_att.GPT) else "gpt")
         dec = model.gpt if self.kind == "caption" else model
@@ -135,6 +147,17 @@ class KVDecoder:
         self.head = bf(dec.lm_head.weight)
         self.blocks = [_block_params(b) for b in tr.h]
         self.cross = [_cross_params(b) for b in tr.h] if self.kind == "cross" else None
+        if self.qdec is not None:
+            if len(self.qdec.blocks) != len(self.blocks) or self.qdec.n_embd != self.wte.shape[1] \
+                    or (self.cross is not None) != (self.qdec.cross is not None):
+                raise ValueError("weights: the quantised decoder was made from another model")
+            for P, Q in zip(self.blocks, self.qdec.blocks):
+                for k in ("attn", "aproj", "fc", "mproj"):
+                    P[k] = (Q[k], P[k][1])
+            if self.cross is not None:
+                for P, Q in zip(self.cross, self.qdec.cross):
+                    for k in ("q", "c"):
+                        P[k] = (Q[k], P[k][1])
         self.block_size = dec.config.block_size
         C = self.wte.shape[1]
         self.C, self.B, self.max_new = C, batch, max_new
@@ -152,6 +175,21 @@ class KVDecoder:
         self.slack = 0      # extra cache columns past prefix + max_new (step_multi: Q of them)
 
     # ---------------------------------------------------------------- pieces
+    def _linear(self, x2, wb, **kw):
+        """The one door to the decoders' linears: wb = (weight, bias or None).  bf16 weights go
+        to K.linear as ever; a gvl.quant.QWeight to gvl_linear_w8 (dequantised first in the
+        prefill and above the kernel's row cap)."""
+        if self.qdec is None:
+            return K.linear(x2, wb[0], wb[1], **kw)
+        qw = wb[0]
+        scr = None
+        if self._dq or x2.shape[0] > K.LINEAR_W8_MAX_ROWS:
+            need = max(qw.q.numel(), self.qdec.scratch_elems())
+            if self._scr is None or self._scr.numel() < need:
+                self._scr = torch.empty(need, dtype=BF16, device=qw.q.device)
+            scr = self._scr
+        return qw.linear(x2, wb[1], scratch=scr, dequant=self._dq, **kw)
+
     def _ln(self, x2, wb):
         return K.layernorm_fwd(x2, wb[0], wb[1], stats=False)[0]
 
@@ -161,7 +199,7 @@ class KVDecoder:
         rows then go through the one-query kernel, as the rows of step() do."""
         P = self.cross[l]
         kvz = self.kvz[l]
-        q = K.linear(self._ln(x2, P["ln"]), *P["q"])
+        q = self._linear(self._ln(x2, P["ln"]), P["q"])
         C = self.C
         if src is not None:
             y = K.attn_decode_beam(q, kvz[:, :, :C], kvz[:, :, C:], P["H"], src)
@@ -170,7 +208,7 @@ class KVDecoder:
         else:
             y = K.attn_fwd(q.view(self.B, S, C), kvz[:, :, :C], kvz[:, :, C:], P["H"], False)[0]
             y = y.view(self.B * S, C)
-        return K.linear(y, P["c"][0], P["c"][1], residual=x2, gate=P["gate"])
+        return self._linear(y, P["c"], residual=x2, gate=P["gate"])
 
     def _attend(self, q, k, v, H, cross):
         """One new query per row over cached keys / values (self-attention cache, or the
@@ -184,13 +222,16 @@ class KVDecoder:
         return [torch.empty(B, self.Tmax, 3 * C, dtype=BF16, device=device) for _ in self.blocks]
 
     def _mlp(self, x2, P):
-        h = K.linear(self._ln(x2, P["ln2"]), *P["fc"], act=1)
-        return K.linear(h, P["mproj"][0], P["mproj"][1], residual=x2)
+        h = self._linear(self._ln(x2, P["ln2"]), P["fc"], act=1)
+        return self._linear(h, P["mproj"], residual=x2)
 
     def _logits(self, x2):
         xf = self._ln(x2, self.lnf)
+        if self.qdec is not None:  # padded to a multiple of 8 rows when it was quantised
+            lg, V = self._linear(xf, (self.qdec.head, None)), self.qdec.head.rows
+            return lg if lg.shape[1] == V else lg[:, :V]
         wp, V = Fn.pad_vocab(self.head)
-        lg = K.linear(xf, wp)
+        lg = self._linear(xf, (wp, None))
         return lg if wp is self.head else lg[:, :V]
 
     # ------------------------------------------------------------------ API
@@ -211,15 +252,19 @@ class KVDecoder:
         self.Tmax = S + self.max_new + self.slack
         self.cache = self._alloc_cache(B, C, x_emb.device)
         x2 = x_emb.to(BF16).reshape(B * S, C).contiguous()
-        for l, P in enumerate(self.blocks):
-            if self.cross is not None:
-                x2 = self._cross(l, x2, S)
-            qkv = K.linear(self._ln(x2, P["ln1"]), *P["attn"])
-            q3 = qkv.view(B, S, 3 * C)
-            self.cache[l][:, :S].copy_(q3)
-            y = K.attn_fwd(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], P["H"], True)[0]
-            x2 = K.linear(y.view(B * S, C), P["aproj"][0], P["aproj"][1], residual=x2)
-            x2 = self._mlp(x2, P)
+        self._dq = self.qdec is not None
+        try:
+            for l, P in enumerate(self.blocks):
+                if self.cross is not None:
+                    x2 = self._cross(l, x2, S)
+                qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
+                q3 = qkv.view(B, S, 3 * C)
+                self.cache[l][:, :S].copy_(q3)
+                y = K.attn_fwd(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], P["H"], True)[0]
+                x2 = self._linear(y.view(B * S, C), P["aproj"], residual=x2)
+                x2 = self._mlp(x2, P)
+        finally:
+            self._dq = False
         self.t = S
         if self.gap_lo is None:
             last = x2.view(B, S, C)[:, S - 1].contiguous()
@@ -251,10 +296,10 @@ class KVDecoder:
             if self.cross is not None:
                 x2 = self._cross(l, x2, 1)
             row = self.cache[l][:, t]  # [B, 3C] view, row stride Tmax*3C
-            K.linear(self._ln(x2, P["ln1"]), *P["attn"], out=row)
+            self._linear(self._ln(x2, P["ln1"]), P["attn"], out=row)
             cl = self.cache[l][:, :t + 1]
             y = self._attend(row[:, :C], cl[:, :, C:2 * C], cl[:, :, 2 * C:], P["H"], False)
-            x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
+            x2 = self._linear(y, P["aproj"], residual=x2)
             x2 = self._mlp(x2, P)
         self.t = t + 1
         return self._logits(x2)
@@ -287,9 +332,9 @@ class KVDecoder:
         for l, P in enumerate(self.blocks):
             if self.cross is not None:
                 x2 = self._cross(l, x2, Q, kv_src)
-            qkv = K.linear(self._ln(x2, P["ln1"]), *P["attn"])
+            qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
             y = K.attn_decode_multi(qkv.view(B, Q, 3 * C), self.cache[l], kv_len, P["H"])
-            x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
+            x2 = self._linear(y, P["aproj"], residual=x2)
             x2 = self._mlp(x2, P)
         return self._logits(x2)
 
@@ -337,8 +382,9 @@ class BeamDecoder(KVDecoder):
     cache_fill: a value to fill the new cache with (a test hook: rows the prefill must not
     write keep it)."""
 
-    def __init__(self, model, batch: int, beams: int, max_new: int, cache_fill=None):
-        super().__init__(model, batch, max_new)
+    def __init__(self, model, batch: int, beams: int, max_new: int, cache_fill=None,
+                 weights=None):
+        super().__init__(model, batch, max_new, weights=weights)
         if not 1 <= beams <= 8:
             raise ValueError(f"beams={beams}: 1..8 supported")
         self.K = beams
@@ -450,7 +496,7 @@ class _Controls:
 def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0, top_k=0,
              top_p=1.0, generator=None, return_logits=False, eos=None, return_lengths=False,
              repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-             penalize_prompt=True, prompt_lens=None, graph=False):
+             penalize_prompt=True, prompt_lens=None, graph=False, weights=None):
     """KV-cached decode of n_new tokens after prompt_ids [B, P].  greedy: argmax (first max);
     else temperature / top-k / top-p sampling with `generator` (a CUDA torch.Generator).
 
@@ -473,18 +519,25 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
 
     graph: replay every token after the first as one captured graph (a GraphedGenerate built for
     this call and closed after it: same results; its docstring says what differs for the
-    generator)."""
+    generator).
+
+    weights: None decodes in bf16 as ever; "int8" quantises the model's block matrices and
+    lm_head (gvl.quant) for this call and runs every linear of it on them (the steps on
+    gvl_linear_w8, the prefill on the dequantised matrices); a gvl.quant.quantize_decoder(model)
+    result does the same without quantising again."""
+    quant.check_weights(weights)
     if graph:
         with GraphedGenerate(model, prompt_ids.shape[1], n_new, greedy=greedy,
                              temperature=temperature, top_k=top_k, top_p=top_p, eos=eos,
                              repetition_penalty=repetition_penalty,
                              no_repeat_ngram_size=no_repeat_ngram_size,
                              min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
-                             penalize_prompt=penalize_prompt, return_logits=return_logits) as ses:
+                             penalize_prompt=penalize_prompt, return_logits=return_logits,
+                             weights=weights) as ses:
             return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, generator=generator,
                        return_lengths=return_lengths)
     B = prompt_ids.shape[0]
-    dec = KVDecoder(model, B, n_new)
+    dec = KVDecoder(model, B, n_new, weights=weights)
     lens = None
     if prompt_lens is not None:
         lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
@@ -526,7 +579,7 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
 def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram=3,
                          draft_ids=None, greedy=False, temperature=1.0, top_k=0, top_p=1.0,
                          generator=None, eos=None, prompt_lens=None, return_lengths=False,
-                         return_stats=False):
+                         return_stats=False, weights=None):
     """generate() with several tokens per decoder pass: draft draft_len (1..7) tokens per row,
     feed [last token, draft] through KVDecoder.step_multi, choose a token from every one of the
     B * (draft_len + 1) logits rows with gvl_sample and keep, per row, the drafted tokens the
@@ -548,7 +601,10 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
     One host read per round (n.min(), to stop once every row is done).  Returns ids
     [B, n_new], then if asked lengths [B] int32, then if asked stats: dict(steps = rounds of
     token choice: one on the prefill's logits, then one per decoder pass (passes = steps - 1),
-    drafted / accepted = int32 [B]: guesses made, and guesses that reached the output)."""
+    drafted / accepted = int32 [B]: guesses made, and guesses that reached the output).
+
+    weights: as in generate()."""
+    quant.check_weights(weights)
     if prompt_ids.dim() != 2 or prompt_ids.shape[0] < 1 or prompt_ids.shape[1] < 1:
         raise ValueError("prompt_ids must be [B, P] with B, P >= 1")
     B, P = prompt_ids.shape
@@ -568,7 +624,7 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
             raise ValueError(f"draft_ids must be integers [B, n_new] = [{B}, {n_new}] "
                              f"(got {draft_ids.dtype} {tuple(draft_ids.shape)})")
     Q = draft_len + 1
-    dec = KVDecoder(model, B, n_new)
+    dec = KVDecoder(model, B, n_new, weights=weights)
     dec.slack = Q
     if prompt_lens is not None:
         lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
@@ -627,7 +683,7 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
 def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
                 return_all=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
                 min_new_tokens=0, bad_tokens=None, penalize_prompt=True, prompt_lens=None,
-                graph=False):
+                graph=False, weights=None):
     """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
     hypotheses per item (prompt_lens: right-padded prompts of different lengths, as in
     generate()).  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
@@ -647,18 +703,21 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     raw scores [B]); return_all: all of them in rank order, [B, K, n_new], [B, K], [B, K].
 
     graph: replay every step after the first as one captured graph (a GraphedBeamSearch built
-    for this call and closed after it: same results)."""
+    for this call and closed after it: same results).
+
+    weights: as in generate()."""
+    quant.check_weights(weights)
     if graph:
         with GraphedBeamSearch(model, prompt_ids.shape[1], n_new, num_beams=num_beams, eos=eos,
                                length_penalty=length_penalty,
                                repetition_penalty=repetition_penalty,
                                no_repeat_ngram_size=no_repeat_ngram_size,
                                min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
-                               penalize_prompt=penalize_prompt) as ses:
+                               penalize_prompt=penalize_prompt, weights=weights) as ses:
             return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, return_all=return_all)
     B, Kb = prompt_ids.shape[0], num_beams
     R = B * Kb
-    dec = BeamDecoder(model, B, Kb, n_new)
+    dec = BeamDecoder(model, B, Kb, n_new, weights=weights)
     lens = None
     if prompt_lens is not None:
         lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
@@ -751,7 +810,9 @@ class _Static:
         return views
 
     def _logits(self, x2):
-        lg = K.linear(self._ln(x2, self.lnf), self.head_p)
+        if self.qdec is not None:
+            return super()._logits(x2)
+        lg = self._linear(self._ln(x2, self.lnf), (self.head_p, None))
         V = self.head.shape[0]
         return lg if self.head_p is self.head else lg[:, :V]
 
@@ -783,10 +844,10 @@ class _Static:
         for l, P in enumerate(self.blocks):
             if self.cross is not None:
                 x2 = self._cross(l, x2, 1)
-            qkv = K.linear(self._ln(x2, P["ln1"]), *P["attn"])
+            qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
             y = K.attn_decode_step(qkv, self.cache[l], t, P["H"], src=self.src,
                                    gap_lo=self.gap_lo, gap_hi=self.gap_hi)
-            x2 = K.linear(y, P["aproj"][0], P["aproj"][1], residual=x2)
+            x2 = self._linear(y, P["aproj"], residual=x2)
             x2 = self._mlp(x2, P)
         return self._logits(x2)
 
@@ -811,12 +872,15 @@ class _GraphedSession:
     (the gap end of prompts of different lengths; the beam table's t0): a call whose S needs
     another value captures its own graph over the same buffers (stats["captures"])."""
 
-    def __init__(self, model, max_prompt, max_new, poll_every):
+    def __init__(self, model, max_prompt, max_new, poll_every, weights=None):
+        quant.check_weights(weights)
         self.max_prompt, self.max_new = int(max_prompt), int(max_new)
         self.poll_every = int(poll_every)
         if self.max_prompt < 1 or self.max_new < 1 or self.poll_every < 1:
             raise ValueError("max_prompt, max_new and poll_every must be at least 1")
         self.model = model
+        # quantised once per session ("int8"), or the caller's snapshot; None: bf16
+        self.weights = quant.resolve_weights(model, weights)
         self.stats = dict(captures=0, replays=0)
         self.dec = None
         self._key = None
@@ -944,8 +1008,8 @@ class GraphedGenerate(_GraphedSession):
     def __init__(self, model, max_prompt, max_new, *, greedy=False, temperature=1.0, top_k=0,
                  top_p=1.0, eos=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
                  min_new_tokens=0, bad_tokens=None, penalize_prompt=True, return_logits=False,
-                 poll_every=8):
-        super().__init__(model, max_prompt, max_new, poll_every)
+                 poll_every=8, weights=None):
+        super().__init__(model, max_prompt, max_new, poll_every, weights)
         if greedy:
             temperature, top_k, top_p = 1.0, 1, 1.0
         self.greedy, self.samp = greedy, (float(temperature), int(top_k), float(top_p))
@@ -1004,7 +1068,7 @@ class GraphedGenerate(_GraphedSession):
         n_new, lens = self._check_call(prompt_ids, n_new, z, prompt_lens)
         B, P = prompt_ids.shape
         if self.dec is None:
-            self.dec = _StaticKV(self.model, B, n_new)
+            self.dec = _StaticKV(self.model, B, n_new, weights=self.weights)
             self.dec._init_static(self.max_prompt, self.max_new)
         dec = self.dec
         dec.max_new = n_new
@@ -1062,8 +1126,8 @@ class GraphedBeamSearch(_GraphedSession):
 
     def __init__(self, model, max_prompt, max_new, *, num_beams=4, eos=50256, length_penalty=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-                 penalize_prompt=True, poll_every=8):
-        super().__init__(model, max_prompt, max_new, poll_every)
+                 penalize_prompt=True, poll_every=8, weights=None):
+        super().__init__(model, max_prompt, max_new, poll_every, weights)
         if not 1 <= num_beams <= 8:
             raise ValueError(f"beams={num_beams}: 1..8 supported")
         self.Kb, self.eos, self.length_penalty = int(num_beams), eos, float(length_penalty)
@@ -1127,7 +1191,7 @@ class GraphedBeamSearch(_GraphedSession):
         Kb, eos = self.Kb, self.eos
         R = B * Kb
         if self.dec is None:
-            self.dec = _StaticBeam(self.model, B, Kb, n_new)
+            self.dec = _StaticBeam(self.model, B, Kb, n_new, weights=self.weights)
             self.dec._init_static(self.max_prompt, self.max_new)
         dec = self.dec
         dec.max_new = n_new

@@ -244,6 +244,95 @@ def linear_dw(dy2, x2, **kw):
     return gemm(dy2, x2, a_mn=True, b_mn=True, **kw)
 
 
+# ------------------------------------------------------- int8 weight-only decoding
+I8 = torch.int8
+LINEAR_W8_MAX_ROWS = _lib.LINEAR_W8_MAX_ROWS
+
+
+def quantize_rows_i8(w, q=None, scale=None):
+    """bf16 w [N, K] -> (int8 q [N, K], fp32 scale [N]): per-row symmetric int8 (gvl.h).  K and
+    the row strides multiples of 8."""
+    _dev(w, q, scale)
+    _rowmajor(w, "w")
+    if w.dtype != BF16:
+        raise TypeError("gvl.quantize_rows_i8: w must be bf16")
+    N, K = w.shape
+    if q is None:
+        q = torch.empty(N, K, dtype=I8, device=w.device)
+    if scale is None:
+        scale = torch.empty(N, dtype=F32, device=w.device)
+    _rowmajor(q, "q")
+    if q.dtype != I8 or scale.dtype != F32 or tuple(q.shape) != (N, K) or \
+            tuple(scale.shape) != (N,) or not scale.is_contiguous():
+        raise ValueError("gvl.quantize_rows_i8: q must be int8 [N, K], scale contiguous fp32 [N]")
+    _lib.check(_L().gvl_quantize_rows_i8(w.data_ptr(), w.stride(0), N, K, q.data_ptr(),
+                                         q.stride(0), scale.data_ptr(), _stream()),
+               "gvl_quantize_rows_i8")
+    return q, scale
+
+
+def dequantize_rows_i8(q, scale, out=None):
+    """int8 q [N, K], fp32 scale [N] -> bf16 [N, K] = bf16(fp32(q) * scale[n])."""
+    _dev(q, scale, out)
+    _rowmajor(q, "q")
+    N, K = q.shape
+    if q.dtype != I8 or scale.dtype != F32 or tuple(scale.shape) != (N,) or \
+            not scale.is_contiguous():
+        raise ValueError("gvl.dequantize_rows_i8: q must be int8 [N, K], scale contiguous fp32 [N]")
+    if out is None:
+        out = torch.empty(N, K, dtype=BF16, device=q.device)
+    _rowmajor(out, "out")
+    if out.dtype != BF16 or tuple(out.shape) != (N, K):
+        raise ValueError("gvl.dequantize_rows_i8: out must be bf16 [N, K]")
+    _lib.check(_L().gvl_dequantize_rows_i8(q.data_ptr(), q.stride(0), scale.data_ptr(), N, K,
+                                           out.data_ptr(), out.stride(0), _stream()),
+               "gvl_dequantize_rows_i8")
+    return out
+
+
+def linear_w8(x2, w, scale=None, bias=None, act=0, residual=None, gate=None, out=None):
+    """y = epi(scale * (x2 @ w.T)) on the kernel for a few rows (gvl_linear_w8): x2 bf16 [M, K],
+    M <= LINEAR_W8_MAX_ROWS; w int8 [N, K] with scale fp32 [N], or (scale None) a bf16 [N, K]
+    weight through the same kernel.  Epilogues: plain, bias, bias + act 1, bias + residual,
+    bias + gate + residual.  Returns y bf16 [M, N]."""
+    _dev(x2, w, scale, bias, residual, gate, out)
+    _rowmajor(x2, "x")
+    _rowmajor(w, "w")
+    if x2.dtype != BF16 or w.dtype != (BF16 if scale is None else I8):
+        raise TypeError("gvl.linear_w8: x must be bf16, w int8 with a scale or bf16 without")
+    M, K = x2.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"gvl.linear_w8: inner dims differ ({K} vs {w.shape[1]})")
+    if scale is not None and (scale.dtype != F32 or tuple(scale.shape) != (N,) or
+                              not scale.is_contiguous()):
+        raise ValueError("gvl.linear_w8: scale must be contiguous fp32 [N]")
+    if bias is not None and (bias.dtype != BF16 or tuple(bias.shape) != (N,) or
+                             not bias.is_contiguous()):
+        raise ValueError("gvl.linear_w8: bias must be contiguous bf16 [N]")
+    if gate is not None and (gate.dtype != BF16 or gate.numel() != 1):
+        raise ValueError("gvl.linear_w8: gate must be one bf16 value")
+    if out is None:
+        out = torch.empty(M, N, dtype=BF16, device=x2.device)
+    _rowmajor(out, "out")
+    if out.dtype != BF16 or tuple(out.shape) != (M, N):
+        raise ValueError("gvl.linear_w8: out must be bf16 [M, N]")
+    if residual is not None:
+        _rowmajor(residual, "residual")
+        if residual.dtype != BF16 or tuple(residual.shape) != (M, N):
+            raise ValueError("gvl.linear_w8: residual must be bf16 [M, N]")
+    d = _lib.LinearW8Desc()
+    d.x, d.w, d.scale, d.c = x2.data_ptr(), w.data_ptr(), _p(scale), out.data_ptr()
+    d.m, d.n, d.k = M, N, K
+    d.ldx, d.ldw, d.ldc = x2.stride(0), w.stride(0), out.stride(0)
+    d.bias, d.act = _p(bias), int(act)
+    d.residual = _p(residual)
+    d.ldr = residual.stride(0) if residual is not None else 0
+    d.gate = _p(gate)
+    _lib.check(_L().gvl_linear_w8(C.byref(d), _stream()), "gvl_linear_w8")
+    return out
+
+
 def gemm_batched(items, *, a_mn=False, b_mn=False, dbias=None):
     """items: [(a, b, out, accumulate)] of one shape and layout: out (+)= op(a) @ op(b) for
     every item as ONE persistent launch (gvl_gemm_batched; falls back to one launch each

@@ -664,6 +664,52 @@ int gvl_gate_bwd_acc_bf16(const void* dx, const void* y, const void* gate, void*
 int gvl_f32_to_bf16(const float* in, void* out, int64_t n, int32_t accumulate,
                     gvl_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Int8 weight-only decoding (csrc/linear_w8.hip).  Format: one fp32 scale per row n of an
+ * nn.Linear weight [N][K], symmetric, no zero point: scale[n] = absmax_n / 127 (one correctly
+ * rounded fp32 division), q[n][k] = clamp(rint(fp32(w[n][k]) / scale[n]), -127, 127) (correctly
+ * rounded division, ties to even); a row of zeros has scale 0 and q 0.  A non-finite weight
+ * makes its row's scale non-finite (the caller checks the scales once).  The dequantised
+ * weight is bf16_rne(fp32(q) * scale[n]).
+ * All three replace the nn.Linear forward inside the reference's decode loops
+ * (source/gpt2/train_gpt2.py:440-449, gpt2_linear/data.py:111-127: model(x) per new token,
+ * whose Linears read every weight once per token). */
+/* bf16 w [N][K] (row stride ldw) -> int8 q [N][K] (ldq), fp32 scale [N]; one launch, 3 bytes of
+ * HBM traffic per weight.  K, ldw, ldq multiples of 8; w, q, scale 16-byte aligned. */
+int gvl_quantize_rows_i8(const void* w, int64_t ldw, int64_t n, int64_t k, void* q, int64_t ldq,
+                         float* scale, gvl_stream_t stream);
+/* int8 q [N][K] (ldq), fp32 scale [N] -> bf16 out [N][K] (ldo).  K, ldq, ldo multiples of 8;
+ * q, scale, out 16-byte aligned. */
+int gvl_dequantize_rows_i8(const void* q, int64_t ldq, const float* scale, int64_t n, int64_t k,
+                           void* out, int64_t ldo, gvl_stream_t stream);
+/* Linear on a few rows: c[m][n] = epi(scale[n] * sum_k x[m][k] * w[n][k]), x bf16 [M][K], w int8
+ * [N][K] with scale fp32 [N]; scale == NULL: w is a bf16 [N][K] weight, same kernel body, no
+ * conversion and no scale.  The int8 values enter the bf16 MFMA exactly, the sum is fp32 (K in
+ * 64-wide chunks dealt to the 8 waves of a workgroup, 32-deep MFMA steps, the waves' partials
+ * added in wave order), the scale is applied once in fp32, then gemm_common.h's epilogue in its
+ * order: +bias, tanh-GELU (act 1), *tanh(*gate), +residual, one rounding to bf16.  Accepted
+ * epilogues: plain; bias; bias + act 1; bias + residual; bias + gate + residual (anything else
+ * is refused).  residual may alias c.
+ * The bits of c[m][n] depend only on row m of x, row n of w, scale[n] and that element's
+ * epilogue operands: not on M, other rows, ldc, or the grid; no atomics, no workspace.
+ * K % 64 == 0, N % 8 == 0, 1 <= M <= GVL_LINEAR_W8_MAX_ROWS (64 rows per pass over w); ldx % 8,
+ * ldw % 16 (int8) or % 8 (bf16), ldc % 4, ldr % 4 == 0, ldc >= N; every operand 16-byte aligned. */
+#define GVL_LINEAR_W8_MAX_ROWS 256
+typedef struct gvl_linear_w8_desc {
+  const void* x;        /* bf16 [M][ldx] */
+  const void* w;        /* int8 [N][ldw] (scale given) or bf16 [N][ldw] (scale NULL) */
+  const float* scale;   /* fp32 [N] or NULL */
+  void* c;              /* bf16 [M][ldc] */
+  int64_t m, n, k;
+  int64_t ldx, ldw, ldc;
+  const void* bias;     /* optional bf16 [N] */
+  int32_t act;          /* 0 none, 1 gelu-tanh */
+  const void* residual; /* optional bf16 [M][ldr], may alias c */
+  int64_t ldr;
+  const void* gate;     /* optional bf16 scalar g: branch *= tanh(g) */
+} gvl_linear_w8_desc;
+int gvl_linear_w8(const gvl_linear_w8_desc* d, gvl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
