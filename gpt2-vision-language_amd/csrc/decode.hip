@@ -52,7 +52,7 @@ struct DecGapP : DecP {
 // empty gap gives the bits of the instance without GAP.  A sequence with every key skipped has
 // l == 0 and writes zeros.
 template <bool IND, bool GAP>
-struct CacheKV {
+struct CacheKV : BF16Elems<CacheKV<IND, GAP>> {
   static constexpr bool may_be_empty = GAP;
   const bf16_t* kb;  // the head's columns of cache row b (IND: of row 0)
   const bf16_t* vb;
@@ -104,7 +104,7 @@ struct StepP {
 // (AppendKV's append, spec.hip).  skip() is CacheKV's.  Every load of the cache in the launch is
 // at a position below tc and every store at tc, so the append races with no load.
 template <bool IND, bool GAP>
-struct StepKV {
+struct StepKV : BF16Elems<StepKV<IND, GAP>> {
   static constexpr bool may_be_empty = GAP;
   bf16_t* cb;        // cache row b (IND: row 0)
   bf16_t* own;       // cache[b, tc]
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_step_kernel(StepP p) {
   const int64_t C3 = 3 * p.C;
   bf16_t* mine = p.cache + b * p.cache_sb;
   const bf16_t* nw = p.qkv + (int64_t)b * C3;
-  StepKV<IND, GAP> kv{IND ? p.cache : mine, mine + tc * C3, nw, tc, p.cache_sb, C3,
+  StepKV<IND, GAP> kv{{}, IND ? p.cache : mine, mine + tc * C3, nw, tc, p.cache_sb, C3,
                       p.C + h * 64, 2 * p.C + h * 64, IND ? p.src + b * p.src_ld : nullptr,
                       (int)gridDim.y - 1, 0, 0};
   if constexpr (GAP) {

@@ -35,7 +35,7 @@ struct MultiP {
 
 // The KV policy (attn_decode.h) of query jq of a sequence with `len` cached positions: position
 // t < len is row t of the cache, position t >= len is row t - len of this step's qkv.
-struct AppendKV {
+struct AppendKV : BF16Elems<AppendKV> {
   static constexpr bool may_be_empty = false;  // a query always attends itself
   bf16_t* cb;        // the sequence's cache rows
   const bf16_t* nw;  // this step's rows of the sequence
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_multi_kernel(MultiP p) {
   const int64_t lmax = min(p.Tmax, (int64_t)DEC_MAXT) - p.Q;
   const int64_t len = min(max((int64_t)p.kv_len[b], (int64_t)0), lmax);
   const bf16_t* nw = p.qkv + (int64_t)b * p.Q * C3;
-  const AppendKV kv{p.cache + b * p.cache_sb, nw, len, C3, p.C + h * 64, 2 * p.C + h * 64, jq};
+  const AppendKV kv{{}, p.cache + b * p.cache_sb, nw, len, C3, p.C + h * 64, 2 * p.C + h * 64, jq};
   attn_decode_body(nw + jq * C3 + h * 64, p.scale, len + jq + 1, kv,
                    p.o + ((int64_t)b * p.Q + jq) * p.o_ld + h * 64);
 }

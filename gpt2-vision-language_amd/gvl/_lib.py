@@ -182,6 +182,10 @@ SIGNATURES = {
     "gvl_quantize_rows_i8": (C.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "gvl_dequantize_rows_i8": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "gvl_linear_w8": (C.c_int, [C.POINTER(LinearW8Desc), c_vp]),
+    "gvl_kv_quantize_i8": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                     c_i64, c_i64, c_vp]),
+    "gvl_attn_decode_q8": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                     c_i64, c_i64, c_i64, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

@@ -59,6 +59,19 @@ token costs one row through each block:
     element of gvl_linear_w8's output has the same bits at any row count, so graph replay, Q = 1
     and speculative decoding keep their equalities in this mode too.
 
+  * int8 KV cache (kv_cache="int8" on KVDecoder, BeamDecoder, generate, beam_search and the
+    graphed sessions; independent of weights=): a layer's cache is kv8 int8 [rows, Tmax, 2C] (k
+    heads, then v heads) with kvs fp32 [rows, Tmax, 2H] (one scale per head vector and position,
+    gvl_quantize_rows_i8's format) instead of bf16 [rows, Tmax, 3C]: 2.125C bytes per position
+    against 6C (kv_cache_bytes), and the q third is not stored.  The prefill quantises its k / v
+    in one launch per layer (gvl_kv_quantize_i8); a step writes c_attn into a [rows, 3C] scratch
+    and gvl_attn_decode_q8 quantises the new k / v into column t and attends: the attention of a
+    step sees, for every position including the step's own, fp32(q8) * scale, and nothing else
+    changes.  step() and step_dev() call the one entry point (the column from the host or from
+    the device), so the graphed calls keep the eager call's bits; beams pass src, prompts of
+    different lengths the gap.  The cross-att model's projected image tokens stay bf16.  Not for
+    speculative decoding (step_multi), whose queries read each other's un-appended keys.
+
 Everything runs on the libgvl kernels; no autograd (inference only).
 """
 from __future__ import annotations
@@ -73,6 +86,23 @@ from . import quant
 from .functional import bf
 
 BF16 = torch.bfloat16
+
+
+def check_kv_cache(kv_cache):
+    """kv_cache: None (the bf16 [rows, Tmax, 3C] cache) or "int8"."""
+    if kv_cache is not None and kv_cache != "int8":
+        raise ValueError(f"kv_cache must be None or 'int8' (got {kv_cache!r})")
+    return kv_cache
+
+
+def kv_cache_bytes(config, rows, Tmax, kv_cache=None):
+    """Bytes of all layers' self-attention caches of a decoder of `config` (n_layer, n_head,
+    n_embd) with `rows` sequences of Tmax columns: 6C per position for the bf16 cache (q | k | v),
+    2C int8 + 2H fp32 = 2.125C for kv_cache="int8".  Host arithmetic only."""
+    check_kv_cache(kv_cache)
+    C, H = int(config.n_embd), int(config.n_head)
+    per_pos = 2 * C + 4 * 2 * H if kv_cache == "int8" else 2 * 3 * C
+    return int(config.n_layer) * int(rows) * int(Tmax) * per_pos
 
 
 def _block_params(blk):
@@ -130,9 +160,12 @@ class KVDecoder:
     With prompt_lens (start) the prompts are right-padded rows of different lengths: see the
     module docstring."""
 
-    def __init__(self, model, batch: int, max_new: int, weights=None):
+    def __init__(self, model, batch: int, max_new: int, weights=None, kv_cache=None):
         from . import caption, cross_att
         self.model = model
+        # kv_cache: None (bf16 [rows, Tmax, 3C] per layer) or "int8" ((kv8, kvs) pairs per layer)
+        self.kv8 = check_kv_cache(kv_cache) == "int8"
+        self.src = None  # BeamDecoder: the table of the step
         # weights: None (bf16), "int8" or a gvl.quant.quantize_decoder(model) result: the whole
         # call then runs the quantised model (gvl.quant; _linear below)
         self.qdec = quant.resolve_weights(model, weights)
@@ -217,9 +250,35 @@ class KVDecoder:
             return K.attn_decode_ragged(q, k, v, H, self.gap_lo, self.gap_hi)
         return K.attn_decode(q, k, v, H)
 
+    def _new_cache(self, rows, C, device, fill=None):
+        """One cache per layer for `rows` sequences: bf16 [rows, Tmax, 3C], or with
+        kv_cache="int8" the pair (kv8 int8 [rows, Tmax, 2C], kvs fp32 [rows, Tmax, 2H]).  fill:
+        a value to fill it with (kv8 takes it cast to int8)."""
+        out = []
+        for P in self.blocks:
+            if self.kv8:
+                c = (torch.empty(rows, self.Tmax, 2 * C, dtype=torch.int8, device=device),
+                     torch.empty(rows, self.Tmax, 2 * P["H"], dtype=torch.float32, device=device))
+                if fill is not None:
+                    c[0].fill_(int(fill))
+                    c[1].fill_(fill)
+            else:
+                c = torch.empty(rows, self.Tmax, 3 * C, dtype=BF16, device=device)
+                if fill is not None:
+                    c.fill_(fill)
+            out.append(c)
+        return out
+
     def _alloc_cache(self, B, C, device):
-        """Per-layer [B, Tmax, 3C] cache tensors the prefill writes."""
-        return [torch.empty(B, self.Tmax, 3 * C, dtype=BF16, device=device) for _ in self.blocks]
+        """Per-layer cache tensors the prefill writes (_new_cache)."""
+        return self._new_cache(B, C, device)
+
+    def _attend_q8(self, qkv, l, t, H):
+        """The new row qkv [rows, 3C] over layer l's int8 cache at column t (an int, or one
+        int32 on the device): gvl_attn_decode_q8 appends and attends."""
+        kv8, kvs = self.cache[l]
+        return K.attn_decode_q8(qkv, kv8, kvs, t, H, src=self.src, gap_lo=self.gap_lo,
+                                gap_hi=self.gap_hi)
 
     def _mlp(self, x2, P):
         h = self._linear(self._ln(x2, P["ln2"]), P["fc"], act=1)
@@ -259,7 +318,10 @@ class KVDecoder:
                     x2 = self._cross(l, x2, S)
                 qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
                 q3 = qkv.view(B, S, 3 * C)
-                self.cache[l][:, :S].copy_(q3)
+                if self.kv8:
+                    K.kv_quantize_i8(q3, *self.cache[l], P["H"])
+                else:
+                    self.cache[l][:, :S].copy_(q3)
                 y = K.attn_fwd(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], P["H"], True)[0]
                 x2 = self._linear(y.view(B * S, C), P["aproj"], residual=x2)
                 x2 = self._mlp(x2, P)
@@ -295,10 +357,14 @@ class KVDecoder:
         for l, P in enumerate(self.blocks):
             if self.cross is not None:
                 x2 = self._cross(l, x2, 1)
-            row = self.cache[l][:, t]  # [B, 3C] view, row stride Tmax*3C
-            self._linear(self._ln(x2, P["ln1"]), P["attn"], out=row)
-            cl = self.cache[l][:, :t + 1]
-            y = self._attend(row[:, :C], cl[:, :, C:2 * C], cl[:, :, 2 * C:], P["H"], False)
+            if self.kv8:
+                qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
+                y = self._attend_q8(qkv, l, t, P["H"])
+            else:
+                row = self.cache[l][:, t]  # [B, 3C] view, row stride Tmax*3C
+                self._linear(self._ln(x2, P["ln1"]), P["attn"], out=row)
+                cl = self.cache[l][:, :t + 1]
+                y = self._attend(row[:, :C], cl[:, :, C:2 * C], cl[:, :, 2 * C:], P["H"], False)
             x2 = self._linear(y, P["aproj"], residual=x2)
             x2 = self._mlp(x2, P)
         self.t = t + 1
@@ -315,6 +381,9 @@ class KVDecoder:
         the rest.  After start(prompt_ids, z, prompt_lens) sequence r begins at
         kv_len = txt0 + len_r and pos = len_r (its new tokens overwrite its pad columns; gap_lo,
         gap_hi and self.t go unused on this path)."""
+        if self.kv8:
+            raise ValueError("kv_cache='int8' is not supported by step_multi / speculative "
+                             "decoding: its queries read each other's un-appended keys")
         B, C = self.rows, self.C
         Q = ids.shape[1]
         if ids.shape[0] != B or not 1 <= Q <= 8:
@@ -383,8 +452,8 @@ class BeamDecoder(KVDecoder):
     write keep it)."""
 
     def __init__(self, model, batch: int, beams: int, max_new: int, cache_fill=None,
-                 weights=None):
-        super().__init__(model, batch, max_new, weights=weights)
+                 weights=None, kv_cache=None):
+        super().__init__(model, batch, max_new, weights=weights, kv_cache=kv_cache)
         if not 1 <= beams <= 8:
             raise ValueError(f"beams={beams}: 1..8 supported")
         self.K = beams
@@ -395,12 +464,11 @@ class BeamDecoder(KVDecoder):
         self.kv_src = None
 
     def _alloc_cache(self, B, C, device):
-        self._full = [torch.empty(B * self.K, self.Tmax, 3 * C, dtype=BF16, device=device)
-                      for _ in self.blocks]
-        if self.cache_fill is not None:
-            for c in self._full:
-                c.fill_(self.cache_fill)
-        return [c.view(B, self.K, self.Tmax, 3 * C)[:, 0] for c in self._full]  # rows b*K
+        self._full = self._new_cache(B * self.K, C, device, self.cache_fill)
+        rows_bk = lambda c: c.view(B, self.K, self.Tmax, c.shape[2])[:, 0]  # rows b*K
+        if self.kv8:
+            return [(rows_bk(c8), rows_bk(cs)) for c8, cs in self._full]
+        return [rows_bk(c) for c in self._full]
 
     def _attend(self, q, k, v, H, cross):
         if self.src is None:  # a one-token prefill of the cross-att model: B plain rows
@@ -496,7 +564,7 @@ class _Controls:
 def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0, top_k=0,
              top_p=1.0, generator=None, return_logits=False, eos=None, return_lengths=False,
              repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-             penalize_prompt=True, prompt_lens=None, graph=False, weights=None):
+             penalize_prompt=True, prompt_lens=None, graph=False, weights=None, kv_cache=None):
     """KV-cached decode of n_new tokens after prompt_ids [B, P].  greedy: argmax (first max);
     else temperature / top-k / top-p sampling with `generator` (a CUDA torch.Generator).
 
@@ -524,8 +592,13 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
     weights: None decodes in bf16 as ever; "int8" quantises the model's block matrices and
     lm_head (gvl.quant) for this call and runs every linear of it on them (the steps on
     gvl_linear_w8, the prefill on the dequantised matrices); a gvl.quant.quantize_decoder(model)
-    result does the same without quantising again."""
+    result does the same without quantising again.
+
+    kv_cache: None keeps the bf16 cache; "int8" stores every layer's keys and values as int8 with
+    one fp32 scale per head vector and position (0.354 of the bytes), and every step's attention
+    then sees fp32(q8) * scale for every position, its own included (the module docstring)."""
     quant.check_weights(weights)
+    check_kv_cache(kv_cache)
     if graph:
         with GraphedGenerate(model, prompt_ids.shape[1], n_new, greedy=greedy,
                              temperature=temperature, top_k=top_k, top_p=top_p, eos=eos,
@@ -533,11 +606,11 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
                              no_repeat_ngram_size=no_repeat_ngram_size,
                              min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
                              penalize_prompt=penalize_prompt, return_logits=return_logits,
-                             weights=weights) as ses:
+                             weights=weights, kv_cache=kv_cache) as ses:
             return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, generator=generator,
                        return_lengths=return_lengths)
     B = prompt_ids.shape[0]
-    dec = KVDecoder(model, B, n_new, weights=weights)
+    dec = KVDecoder(model, B, n_new, weights=weights, kv_cache=kv_cache)
     lens = None
     if prompt_lens is not None:
         lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
@@ -579,7 +652,7 @@ def generate(model, prompt_ids, n_new, *, z=None, greedy=False, temperature=1.0,
 def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram=3,
                          draft_ids=None, greedy=False, temperature=1.0, top_k=0, top_p=1.0,
                          generator=None, eos=None, prompt_lens=None, return_lengths=False,
-                         return_stats=False, weights=None):
+                         return_stats=False, weights=None, kv_cache=None):
     """generate() with several tokens per decoder pass: draft draft_len (1..7) tokens per row,
     feed [last token, draft] through KVDecoder.step_multi, choose a token from every one of the
     B * (draft_len + 1) logits rows with gvl_sample and keep, per row, the drafted tokens the
@@ -603,8 +676,11 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
     token choice: one on the prefill's logits, then one per decoder pass (passes = steps - 1),
     drafted / accepted = int32 [B]: guesses made, and guesses that reached the output).
 
-    weights: as in generate()."""
+    weights: as in generate().  kv_cache: None only; "int8" is refused (the queries of a pass
+    read each other's un-appended keys, which the int8 cache's attention does not serve)."""
     quant.check_weights(weights)
+    if check_kv_cache(kv_cache) is not None:
+        raise ValueError("kv_cache='int8' is not supported by speculative_generate")
     if prompt_ids.dim() != 2 or prompt_ids.shape[0] < 1 or prompt_ids.shape[1] < 1:
         raise ValueError("prompt_ids must be [B, P] with B, P >= 1")
     B, P = prompt_ids.shape
@@ -683,7 +759,7 @@ def speculative_generate(model, prompt_ids, n_new, *, z=None, draft_len=4, ngram
 def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, length_penalty=1.0,
                 return_all=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
                 min_new_tokens=0, bad_tokens=None, penalize_prompt=True, prompt_lens=None,
-                graph=False, weights=None):
+                graph=False, weights=None, kv_cache=None):
     """KV-cached beam search of up to n_new tokens after prompt_ids [B, P] with num_beams (<= 8)
     hypotheses per item (prompt_lens: right-padded prompts of different lengths, as in
     generate()).  A hypothesis' raw score is the sum of the fp32 log-probabilities of its
@@ -705,19 +781,21 @@ def beam_search(model, prompt_ids, n_new, *, z=None, num_beams=4, eos=50256, len
     graph: replay every step after the first as one captured graph (a GraphedBeamSearch built
     for this call and closed after it: same results).
 
-    weights: as in generate()."""
+    weights, kv_cache: as in generate()."""
     quant.check_weights(weights)
+    check_kv_cache(kv_cache)
     if graph:
         with GraphedBeamSearch(model, prompt_ids.shape[1], n_new, num_beams=num_beams, eos=eos,
                                length_penalty=length_penalty,
                                repetition_penalty=repetition_penalty,
                                no_repeat_ngram_size=no_repeat_ngram_size,
                                min_new_tokens=min_new_tokens, bad_tokens=bad_tokens,
-                               penalize_prompt=penalize_prompt, weights=weights) as ses:
+                               penalize_prompt=penalize_prompt, weights=weights,
+                               kv_cache=kv_cache) as ses:
             return ses(prompt_ids, n_new, z=z, prompt_lens=prompt_lens, return_all=return_all)
     B, Kb = prompt_ids.shape[0], num_beams
     R = B * Kb
-    dec = BeamDecoder(model, B, Kb, n_new, weights=weights)
+    dec = BeamDecoder(model, B, Kb, n_new, weights=weights, kv_cache=kv_cache)
     lens = None
     if prompt_lens is not None:
         lens = check_prompt_lens(prompt_ids, prompt_lens, n_new, dec.block_size)
@@ -845,8 +923,11 @@ class _Static:
             if self.cross is not None:
                 x2 = self._cross(l, x2, 1)
             qkv = self._linear(self._ln(x2, P["ln1"]), P["attn"])
-            y = K.attn_decode_step(qkv, self.cache[l], t, P["H"], src=self.src,
-                                   gap_lo=self.gap_lo, gap_hi=self.gap_hi)
+            if self.kv8:
+                y = self._attend_q8(qkv, l, t, P["H"])
+            else:
+                y = K.attn_decode_step(qkv, self.cache[l], t, P["H"], src=self.src,
+                                       gap_lo=self.gap_lo, gap_hi=self.gap_hi)
             x2 = self._linear(y, P["aproj"], residual=x2)
             x2 = self._mlp(x2, P)
         return self._logits(x2)
@@ -872,8 +953,9 @@ class _GraphedSession:
     (the gap end of prompts of different lengths; the beam table's t0): a call whose S needs
     another value captures its own graph over the same buffers (stats["captures"])."""
 
-    def __init__(self, model, max_prompt, max_new, poll_every, weights=None):
+    def __init__(self, model, max_prompt, max_new, poll_every, weights=None, kv_cache=None):
         quant.check_weights(weights)
+        self.kv_cache = check_kv_cache(kv_cache)
         self.max_prompt, self.max_new = int(max_prompt), int(max_new)
         self.poll_every = int(poll_every)
         if self.max_prompt < 1 or self.max_new < 1 or self.poll_every < 1:
@@ -1008,8 +1090,8 @@ class GraphedGenerate(_GraphedSession):
     def __init__(self, model, max_prompt, max_new, *, greedy=False, temperature=1.0, top_k=0,
                  top_p=1.0, eos=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
                  min_new_tokens=0, bad_tokens=None, penalize_prompt=True, return_logits=False,
-                 poll_every=8, weights=None):
-        super().__init__(model, max_prompt, max_new, poll_every, weights)
+                 poll_every=8, weights=None, kv_cache=None):
+        super().__init__(model, max_prompt, max_new, poll_every, weights, kv_cache)
         if greedy:
             temperature, top_k, top_p = 1.0, 1, 1.0
         self.greedy, self.samp = greedy, (float(temperature), int(top_k), float(top_p))
@@ -1068,7 +1150,8 @@ class GraphedGenerate(_GraphedSession):
         n_new, lens = self._check_call(prompt_ids, n_new, z, prompt_lens)
         B, P = prompt_ids.shape
         if self.dec is None:
-            self.dec = _StaticKV(self.model, B, n_new, weights=self.weights)
+            self.dec = _StaticKV(self.model, B, n_new, weights=self.weights,
+                                 kv_cache=self.kv_cache)
             self.dec._init_static(self.max_prompt, self.max_new)
         dec = self.dec
         dec.max_new = n_new
@@ -1126,8 +1209,8 @@ class GraphedBeamSearch(_GraphedSession):
 
     def __init__(self, model, max_prompt, max_new, *, num_beams=4, eos=50256, length_penalty=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, bad_tokens=None,
-                 penalize_prompt=True, poll_every=8, weights=None):
-        super().__init__(model, max_prompt, max_new, poll_every, weights)
+                 penalize_prompt=True, poll_every=8, weights=None, kv_cache=None):
+        super().__init__(model, max_prompt, max_new, poll_every, weights, kv_cache)
         if not 1 <= num_beams <= 8:
             raise ValueError(f"beams={num_beams}: 1..8 supported")
         self.Kb, self.eos, self.length_penalty = int(num_beams), eos, float(length_penalty)
@@ -1191,7 +1274,8 @@ class GraphedBeamSearch(_GraphedSession):
         Kb, eos = self.Kb, self.eos
         R = B * Kb
         if self.dec is None:
-            self.dec = _StaticBeam(self.model, B, Kb, n_new, weights=self.weights)
+            self.dec = _StaticBeam(self.model, B, Kb, n_new, weights=self.weights,
+                                   kv_cache=self.kv_cache)
             self.dec._init_static(self.max_prompt, self.max_new)
         dec = self.dec
         dec.max_new = n_new

@@ -697,6 +697,89 @@ def attn_decode_step(qkv, cache, t, H, src=None, gap_lo=None, gap_hi=0, out=None
     return out
 
 
+def _kv8_pair(kv8, kvs, rows, H, who):
+    """The checks an int8 cache pair shares: kv8 int8 [rows, Tmax, 2C] and kvs fp32
+    [rows, Tmax, 2H] with contiguous [Tmax, .] rows (the sequence strides are free).  -> Tmax"""
+    C = H * 64
+    if kv8.dim() != 3 or kvs.dim() != 3 or kv8.dtype != I8 or kvs.dtype != F32:
+        raise ValueError(f"gvl: {who} takes kv8 int8 [rows, Tmax, 2C] and kvs fp32 [rows, Tmax, 2H]")
+    Tmax = kv8.shape[1]
+    if (tuple(kv8.shape) != (rows, Tmax, 2 * C) or tuple(kvs.shape) != (rows, Tmax, 2 * H) or
+            kv8.stride(2) != 1 or kvs.stride(2) != 1 or kv8.stride(1) != 2 * C or
+            kvs.stride(1) != 2 * H):
+        raise ValueError(f"gvl: {who}: kv8 must be [{rows}, Tmax, {2 * C}] and kvs "
+                         f"[{rows}, Tmax, {2 * H}] with contiguous rows")
+    return Tmax
+
+
+def _sb(t, row_elems):
+    """Sequence stride of a [rows, T, cols] tensor (one sequence: torch may report any)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), row_elems)
+
+
+def kv_quantize_i8(qkv, kv8, kvs, H, col0=0):
+    """Quantise the k and v thirds of qkv bf16 [B, S, 3C] (a c_attn output, C = H*64; any
+    sequence / position strides) into columns [col0, col0 + S) of an int8 cache pair
+    (include/gvl.h gvl_kv_quantize_i8): kv8 int8 [B, Tmax, 2C], kvs fp32 [B, Tmax, 2H]."""
+    _dev(qkv, kv8, kvs)
+    C = H * 64
+    if qkv.dim() != 3 or qkv.dtype != BF16 or qkv.shape[2] != 3 * C or qkv.stride(2) != 1:
+        raise ValueError("gvl: kv_quantize_i8 takes qkv bf16 [B, S, 3 * H * 64] with contiguous rows")
+    B, S, _ = qkv.shape
+    Tmax = _kv8_pair(kv8, kvs, B, H, "kv_quantize_i8")
+    col0 = int(col0)
+    if not 0 <= col0 <= Tmax - S:
+        raise ValueError(f"gvl: col0 = {col0} + S = {S} outside the cache's {Tmax} columns")
+    st = qkv.stride(1) if S > 1 else max(qkv.stride(1), 3 * C)
+    _lib.check(_L().gvl_kv_quantize_i8(qkv.data_ptr(), _sb(qkv, S * st), st, kv8.data_ptr(),
+                                       _sb(kv8, Tmax * 2 * C), kvs.data_ptr(),
+                                       _sb(kvs, Tmax * 2 * H), B, S, H, col0, _stream()),
+               "gvl_kv_quantize_i8")
+    return kv8, kvs
+
+
+def attn_decode_q8(qkv, kv8, kvs, t, H, src=None, gap_lo=None, gap_hi=0, out=None, scale=None):
+    """One new query per sequence over an int8 cache pair, the quantising append fused
+    (include/gvl.h gvl_attn_decode_q8).  qkv bf16 [R, 3C] contiguous (this step's c_attn output);
+    kv8 int8 [R, Tmax, 2C], kvs fp32 [R, Tmax, 2H]; t: the column of the step, a Python int or one
+    int32 on the device (graph replay).  Sequence r attends positions [0, t], every one as
+    fp32(q8) * scale, and its quantised k / v land in column t.  src, gap_lo, gap_hi: as in
+    attn_decode_step.  -> o [R, C]."""
+    t_dev = t if isinstance(t, torch.Tensor) else None
+    _dev(qkv, kv8, kvs, t_dev, src, gap_lo)
+    if qkv.dim() != 2:
+        raise ValueError("gvl: attn_decode_q8 takes qkv [R, 3C]")
+    R, C3 = qkv.shape
+    C = H * 64
+    if qkv.dtype != BF16 or C3 != 3 * C or not qkv.is_contiguous():
+        raise ValueError("gvl: qkv must be a contiguous bf16 [R, 3 * H * 64] tensor")
+    Tmax = _kv8_pair(kv8, kvs, R, H, "attn_decode_q8")
+    if t_dev is not None:
+        _dev_scalar(t_dev, "t")
+    if src is not None:
+        _rowmajor(src, "src")
+        if src.dtype != torch.int32 or src.shape[0] != R or src.shape[1] < Tmax:
+            raise ValueError("gvl: src must be an int32 [R, >= Tmax] table")
+    if gap_lo is not None:
+        _i32_vec(gap_lo, R, "gap_lo")
+        if not 0 <= int(gap_hi) <= Tmax:
+            raise ValueError(f"gvl: gap_hi = {gap_hi} outside 0..Tmax = {Tmax}")
+    if out is None:
+        out = torch.empty(R, C, dtype=BF16, device=qkv.device)
+    elif out.dtype != BF16 or out.shape != (R, C) or out.stride(1) != 1:
+        raise ValueError("gvl: attn_decode_q8 writes a bf16 [R, C] row-major tensor")
+    if scale is None:
+        scale = _DECODE_SCALE
+    _lib.check(_L().gvl_attn_decode_q8(qkv.data_ptr(), kv8.data_ptr(), _sb(kv8, Tmax * 2 * C),
+                                       kvs.data_ptr(), _sb(kvs, Tmax * 2 * H), Tmax,
+                                       0 if t_dev is not None else int(t), _p(t_dev),
+                                       out.data_ptr(), _ld(out), R, H, float(scale), _p(src),
+                                       0 if src is None else _ld(src), _p(gap_lo),
+                                       int(gap_hi) if gap_lo is not None else 0, _stream()),
+               "gvl_attn_decode_q8")
+    return out
+
+
 def ngram_draft(prompt, plen, emitted, n, ngram, D, given=None, out=None):
     """Prompt-lookup draft (include/gvl.h gvl_ngram_draft): prompt int64 [B, P], plen int32 [B],
     emitted int64 [B, n_new] of which row b holds n[b] tokens (n int32 [B]), given optional int64

@@ -710,6 +710,49 @@ typedef struct gvl_linear_w8_desc {
 } gvl_linear_w8_desc;
 int gvl_linear_w8(const gvl_linear_w8_desc* d, gvl_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Int8 KV cache for decoding (csrc/attn_decode_q8.hip).  New symbols at ABI v14 without a version
+ * bump, like the beam, ragged, step and w8 entry points.  The format is gvl_quantize_rows_i8's
+ * with one "row" being one head's 64-wide key or value vector at one position: scale = absmax /
+ * 127, q = clamp(rint(x / scale), -127, 127), a zero vector has scale 0 and q 0, a non-finite
+ * element makes the scale non-finite.  A layer's cache is two tensors, C = H*64:
+ *   kv8 int8 [R][Tmax][2C] (rows 2C apart, sequences kv8_sb apart): the k heads, then the v heads;
+ *   kvs fp32 [R][Tmax][2H] (rows 2H apart, sequences kvs_sb apart): the k scales, then the v scales.
+ * The q third of a c_attn row is not stored.
+ *
+ * gvl_kv_quantize_i8 (the prefill): the k and v thirds of qkv[b][s] (bf16 [B][S][3C], sequences
+ * qkv_sb apart, positions qkv_st apart) go to column col0 + s of sequence b, for all B * S
+ * positions in one launch.  Nothing else is written.  0 <= col0, col0 + S <= 4096; kv8_sb and
+ * kvs_sb at least col0 + S rows; kv8 16-byte aligned.
+ *
+ * gvl_attn_decode_q8 (a step): append + attend.  qkv is this step's contiguous c_attn output
+ * [R][3C]; the column of the step is tc = *t_dev when t_dev (one int32 on the device: graph replay)
+ * is given, else t.  The workgroup of (sequence r, head h) quantises that head's new k and v of
+ * qkv[r], stores the 64 + 64 bytes and the two scales to column tc of row r, and attends positions
+ * [0, tc]: position t' < tc from cache row r, or from row src[r*src_ld + t'] when src (int32,
+ * src_ld >= Tmax, entries clamped into [0, R)) is given; position tc is its own quantised vectors,
+ * kept on chip.  With gap_lo (int32 [R], clamped into [0, gap_hi]; 0 <= gap_hi <= Tmax) positions
+ * [gap_lo[r], gap_hi) are left out as in gvl_attn_decode_ragged: neither their bytes nor their
+ * scales are loaded, and a sequence with every position skipped writes zeros.
+ *   Semantics: the attention sees, for every position including the step's own, fp32(q8) * scale;
+ *   nothing else differs from gvl_attn_decode_step.  score_t = ks[t] * sum_d qs[d] * fp32(kq[t][d])
+ *   (the sum in fp32, the scale applied once after it), the value pass accumulates
+ *   (p_t * vs[t]) * fp32(vq[t][d]); max, sum, skip and the final division are attn_decode_body's.
+ *   Bit properties (one kernel body, four (src, gap) instances): the bytes and scales appended
+ *   equal what gvl_kv_quantize_i8 writes for the same qkv; src = identity and an empty gap each
+ *   give the bits of the instance without them; t_dev gives the bits of the same column passed as t.
+ *   Every load of the cache is at a position below tc, every store at tc.  tc outside
+ *   [0, Tmax) makes the call a no-op: neither o nor the cache is written.  1 <= Tmax <= 4096.
+ * Both check on the host what the host can see (-1 and gvl_last_error naming the argument) and are
+ * capturable: no allocation, no synchronisation. */
+int gvl_kv_quantize_i8(const void* qkv, int64_t qkv_sb, int64_t qkv_st, void* kv8, int64_t kv8_sb,
+                       float* kvs, int64_t kvs_sb, int64_t B, int64_t S, int64_t H, int64_t col0,
+                       gvl_stream_t stream);
+int gvl_attn_decode_q8(const void* qkv, void* kv8, int64_t kv8_sb, float* kvs, int64_t kvs_sb,
+                       int64_t Tmax, int64_t t, const int32_t* t_dev, void* o, int64_t o_ld,
+                       int64_t R, int64_t H, float scale, const int32_t* src, int64_t src_ld,
+                       const int32_t* gap_lo, int64_t gap_hi, gvl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
